@@ -1,23 +1,31 @@
 """bench.py -- RIDERS training throughput on MI355X: BASELINE.json's metric "train imgs/sec (RC-Net+SML, 256x512)".
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Headline (`--workload chain`, the default): ONE timed loop whose iteration carries 16 synthetic 256x512 images through BOTH training stages --
 two RC-Net optimisation steps (BASELINE configs[1]: batch 8, K = 30 radar points, patch 240x100, image edge-padded to 496x612) followed by one
 Scale-Map-Learner optimisation step (configs[2]: batch 16) -- each step = normalise + labels / device pre-step + forward + loss + backward +
 (RCCL gradient all-reduce for N > 1, started per stage while the backward is still running) + fused Adam, inputs resident in HBM, bf16.
-`value` = 16 x K x N / elapsed, `ms_per_step` = one iteration.  The two stages are then timed on their own the same way (sub-objects `rcnet`,
-`sml`); `--workload rcnet` / `sml` run one stage only (tools, profiler children).  Weak scaling: every rank processes its own images.
+`value` = 16 x K x N / elapsed, `ms_per_step` = one iteration.  With `--full` the two stages are then timed on their own the same way
+(sub-objects `rcnet`, `sml`); `--workload rcnet` / `sml` run one stage only (tools, profiler children).  Weak scaling: every rank processes
+its own images.
 
-Timing: W warm-up iterations, then untimed "settling" replays until `--settle-seconds` of GPU work have passed (clocks and the SMI sampler
-settle), then EXACTLY K timed iterations between barrier + synchronize pairs, max over ranks.
+Timing: W warm-up iterations, then (default with `--full` only) untimed "settling" replays until `--settle-seconds` of GPU work have passed
+(clocks and the SMI sampler settle), then EXACTLY K timed iterations between barrier + synchronize pairs, max over ranks.
+
+`--dump-outputs DIR`: what the last timed step handed back, per stage: loss, updated parameters, their gradients, BatchNorm buffers, as
+DIR/<stage>_<name>.npy (float32; parameters and gradients above 2^21 elements as a fixed seeded sample, <name>_sample.npy).  Inputs and
+initial weights are seeded, so the same arguments give the same inputs on every run and build.
+
+A plain run (no `--full`) does only what the headline needs: set up, warm up, time, dump, print the line.  Everything below the line's
+headline fields is measured with `--full` only.
 
 Launching: with WORLD_SIZE in the environment (torch.distributed.run) this process is one rank and `--gpus` must equal WORLD_SIZE (exit 2
 otherwise).  Without it, `--gpus N` (N > 1) makes THIS process a GPU-free parent that starts N rank processes before anything touches a GPU,
 relays rank 0's JSON line and exits with the worst rank's code.
 
-Rank 0 prints ONE JSON line (< 6 KB; everything else goes to --full-json), including
+Rank 0 prints ONE JSON line (< 6 KB; with --full everything else goes to --full-json), with --full including
   "roofline":      the dominant kernel FAMILY of the RC-Net step (all instantiations of one kernel template, e.g. conv3x3_frag_kernel): achieved =
                    algorithmic FLOPs (2 / MAC) or bytes (every operand once) of its launches / their summed durations.  Durations: HIP events
                    on the launch stream in instrumented eager steps right after the timed region (`avg_launch_us_hip_events`) AND the rocprofv3
@@ -49,6 +57,7 @@ PEAK_MFMA = {"fp32": 157.3, "bf16": 2500.0, "fp16": 2500.0}       # TFLOP/s dens
 KSTATS_FILE = "profiles/r06_%s_kernel_stats.csv"                     # rocprofv3 --kernel-trace --stats summary of the same command
 RIDGE = {k: v * 1e12 / (PEAK_HBM * 1e9) for k, v in PEAK_MFMA.items()}     # FLOP/B above which the MFMA roof binds
 CHAIN_RC_STEPS = 2      # RC-Net steps (batch 8) per SML step (batch 16): the same 16 images pass both stages
+DUMP_SAMPLE = 1 << 21   # --dump-outputs: elements kept of a larger array (a fixed seeded sample): at most 4 x 8 MB of parameters and gradients per run
 
 
 # ================================================================================================ CPU baseline (oracle = test infrastructure)
@@ -357,7 +366,7 @@ def _child_base(args, workload, outdir, steps=2, warmup=1, eager=True, settle=0.
     base = ["python3", os.path.abspath(__file__), "--workload", workload, "--steps", str(steps), "--warmup", str(warmup), "--settle-seconds", str(settle),
             "--no-cpu-baseline", "--no-legs", "--no-children", "--batch", str(args.batch), "--dtype", args.dtype, "--height", str(args.height),
             "--width", str(args.width), "--sml-batch", str(args.sml_batch), "--sml-height", str(args.sml_height), "--sml-width", str(args.sml_width),
-            "--full-json", os.path.join(outdir, "child_full.json")]
+            "--full-json", os.path.join(outdir, "child_full.json"), "--full"]
     if eager:
         base.append("--eager")
     if getattr(args, "autograph", False):
@@ -570,8 +579,9 @@ def full_record(args, world, comm, ddp, head, rc, sml, legs, cpu, val, caller=No
     wl = args.workload
     if wl == "chain":
         per = head["images_per_step"]
+        rg, sg = rc or head["stages"]["rcnet"], sml or head["stages"]["sml"]      # (stage geometry when the stages were not timed on their own)
         workload = ("%d RC-Net steps (batch %d, K=30, patch 240x100, %dx%d) + 1 SML step (batch %d, %dx%d) per iteration = %d images through BOTH stages; "
-                    "each step fwd+loss+bwd+Adam" % (CHAIN_RC_STEPS, rc["batch_per_gpu"], rc["height"], rc["width"], sml["batch_per_gpu"], sml["height"], sml["width"], per))
+                    "each step fwd+loss+bwd+Adam" % (CHAIN_RC_STEPS, rg["batch_per_gpu"], rg["height"], rg["width"], sg["batch_per_gpu"], sg["height"], sg["width"], per))
     else:
         per = head["batch_per_gpu"]
         workload = leg_workload("sml" if wl.endswith("sml") else "rcnet", head) + (" (unchanged caller: eager, torch.optim.Adam)" if wl.startswith("caller") else "")
@@ -591,11 +601,11 @@ def full_record(args, world, comm, ddp, head, rc, sml, legs, cpu, val, caller=No
         "roofline": src.get("roofline"), "roofline_families": src.get("roofline_families"), "roofline_kernel": src.get("roofline_kernel"),
         "roofline_workload": "the RC-Net step" if (wl == "chain" or wl.endswith("rcnet")) else "the SML step",
     }
-    if wl == "chain":
+    if wl == "chain" and rc is not None and sml is not None:
         out["rcnet"] = leg_record("rcnet", rc, dt)
         out["sml"] = leg_record("sml", sml, dt)
         out["chain_vs_parts"] = {"chain_ms": head["ms_per_step"], "parts_ms": CHAIN_RC_STEPS * rc["ms_per_step"] + sml["ms_per_step"]}
-    else:
+    elif wl != "chain":
         for k in ("kernels", "families", "launches_per_step", "kernel_ms_per_step"):
             if head.get(k) is not None:
                 out[k] = head[k]
@@ -742,6 +752,37 @@ def close_leg(L):
     torch.cuda.empty_cache()
 
 
+def leg_outputs(kind, model, opt, loss):
+    """What a caller of one stage's training step receives after it: the loss, the updated parameters and their gradients (FlatAdam's arenas:
+    16-byte aligned slots with zero padding; otherwise the parameters in order) and the floating-point BatchNorm buffers -> {name: tensor}"""
+    nets = [model._unwrap(model.encoder), model._unwrap(model.decoder)] if kind == "rcnet" else [model]
+    if hasattr(opt, "flat_param"):
+        w, g = opt.flat_param, opt.flat_grad
+    else:
+        params = list(model.parameters())
+        w = torch.cat([p.detach().reshape(-1) for p in params])
+        g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    out = {kind + "_params": w, kind + "_grads": g,
+           kind + "_buffers": torch.cat([b.detach().reshape(-1).float() for net in nets for b in net.buffers() if b.is_floating_point()])}
+    if loss is not None:
+        out[kind + "_loss"] = loss.detach().reshape(-1)
+    return out
+
+
+def dump_outputs(outdir, arrays):
+    """{name: tensor} -> outdir/<name>.npy in float32; an array above DUMP_SAMPLE elements is written as the same seeded sample of its elements
+    every run (outdir/<name>_sample.npy, indices ascending)"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1).float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t, name = t[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+
 def _barrier(world):
     if world > 1:
         import torch.distributed as dist
@@ -807,8 +848,8 @@ def instrument(L, n=3):
     return timer, n
 
 
-def measure_leg(L, steps, warmup, settle_seconds, world, rank, dev, prof_children=False):
-    """warm-up, settle, timed region, instrumented steps, rooflines of one leg -> dict"""
+def measure_leg(L, steps, warmup, settle_seconds, world, rank, dev, prof_children=False, dump=None):
+    """warm-up, settle, timed region (its last step's outputs to `dump`), and with --full the instrumented steps and rooflines of one leg -> dict"""
     from riders_amd import engine
     args = L.args
     loss = None
@@ -816,7 +857,7 @@ def measure_leg(L, steps, warmup, settle_seconds, world, rank, dev, prof_childre
         loss = L.step()
     nset = settle(L.step, settle_seconds, world, dev)
     timer = None
-    if args.eager and not args.step_markers:
+    if args.full and args.eager and not args.step_markers:
         timer = engine.KernelTimer(repeat=1)
         engine.set_kernel_timer(timer)
     if args.step_markers:      # profiler child: every step bracketed by the marker kernel (kernel_trace_child counts the dispatches in between)
@@ -829,11 +870,15 @@ def measure_leg(L, steps, warmup, settle_seconds, world, rank, dev, prof_childre
     else:
         elapsed, loss = timed(L.step, steps, world, dev)
     engine.set_kernel_timer(None)
+    if dump:
+        dump_outputs(dump, leg_outputs(L.kind, L.model, L.opt, loss))
     final_loss = float(loss.detach()) if loss is not None else float('nan')
     engine.check_roi_overflow()      # raises if a timed step met a RoI geometry the one-byte arg-max cannot encode (its gradients would be NaN)
     ms = elapsed * 1e3 / max(steps, 1)
     out = dict(value=L.batch_n * world * steps / elapsed, ms_per_step=ms, steps=steps, warmup=warmup, settle_steps=nset, final_loss=final_loss,
                batch_per_gpu=L.batch_n, height=L.h, width=L.w, launch_mode=L.launch_mode)
+    if not args.full:
+        return out
     tsteps = steps
     if timer is None and not args.step_markers:
         # EVERY rank runs the instrumented eager steps: with a reducer they contain collectives (a rank-0-only pass would wait for its peers forever)
@@ -859,34 +904,39 @@ def measure_leg(L, steps, warmup, settle_seconds, world, rank, dev, prof_childre
     return out
 
 
-def run_workload(kind, args, dev, world, rank, steps, warmup, prof_children=False, **override):
+def run_workload(kind, args, dev, world, rank, steps, warmup, prof_children=False, dump=None, **override):
     """one stage on its own: build, measure, tear down"""
     from riders_amd import engine
     engine.clear_caches()
     L = build_leg(kind, args, dev, world, rank, **override)
     try:
-        return measure_leg(L, steps, warmup, L.args.settle_seconds, world, rank, dev, prof_children)
+        return measure_leg(L, steps, warmup, L.args.settle_seconds, world, rank, dev, prof_children, dump)
     finally:
         close_leg(L)
         engine.set_param_grad_allocator(None)
 
 
-def run_chain(args, dev, world, rank, steps, warmup):
+def run_chain(args, dev, world, rank, steps, warmup, dump=None):
     """BASELINE.json's metric: both stages alive in one process, ONE timed loop of (2 RC-Net steps + 1 SML step) = 16 images through both
-    stages per iteration; then each stage timed on its own (same models, same graphs).  -> (chain, rcnet, sml) dicts"""
+    stages per iteration; with --full each stage is then timed on its own (same models, same graphs).  -> (chain, rcnet, sml) dicts (the
+    last two None without --full)"""
     from riders_amd import engine
     engine.clear_caches()
     rc = build_leg("rcnet", args, dev, world, rank)
     sm = build_leg("sml", args, dev, world, rank)
     try:
+        last = {}
+
         def it():
             for _ in range(CHAIN_RC_STEPS):
-                rc.step()
+                last["rcnet"] = rc.step()
             return sm.step()
         for _ in range(warmup):
             it()
         nset = settle(it, args.settle_seconds, world, dev)
         elapsed, loss = timed(it, steps, world, dev)
+        if dump:
+            dump_outputs(dump, dict(leg_outputs("rcnet", rc.model, rc.opt, last.get("rcnet")), **leg_outputs("sml", sm.model, sm.opt, loss)))
         per = CHAIN_RC_STEPS * rc.batch_n
         if per != sm.batch_n:
             sys.stderr.write("bench.py: chain: %d RC-Net images vs %d SML images per iteration -- value counts the smaller\n" % (per, sm.batch_n))
@@ -894,7 +944,10 @@ def run_chain(args, dev, world, rank, steps, warmup):
         engine.check_roi_overflow()
         chain = dict(value=per * world * steps / elapsed, ms_per_step=elapsed * 1e3 / max(steps, 1), steps=steps, warmup=warmup, settle_steps=nset,
                      final_loss=float(loss.detach()), images_per_step=per, batch_per_gpu=per, height=rc.h, width=rc.w,
-                     launch_mode="per stage: " + rc.launch_mode)
+                     launch_mode="per stage: " + rc.launch_mode,
+                     stages=dict(rcnet=dict(batch_per_gpu=rc.batch_n, height=rc.h, width=rc.w), sml=dict(batch_per_gpu=sm.batch_n, height=sm.h, width=sm.w)))
+        if not args.full:
+            return chain, None, None
         r_rc = measure_leg(rc, steps, 0, min(args.settle_seconds, 1.0), world, rank, dev, prof_children=(world == 1 and not args.no_children))
         sm.args = argparse.Namespace(**dict(vars(sm.args), no_live_traffic=True))      # (kernel trace only for the SML stage: its counter passes would add ~1 min)
         r_sm = measure_leg(sm, steps, 0, min(args.settle_seconds, 1.0), world, rank, dev, prof_children=(world == 1 and not args.no_children))
@@ -904,7 +957,7 @@ def run_chain(args, dev, world, rank, steps, warmup):
         engine.set_param_grad_allocator(None)
 
 
-def run_unchanged_caller(kind, args, dev, steps, warmup=3, autograph=False):
+def run_unchanged_caller(kind, args, dev, steps, warmup=3, autograph=False, dump=None):
     """The path the reference's unmodified training loop takes through the aliased modules: per step the label build /
     device pre-step, model.forward, compute_loss, optimizer.zero_grad(), loss.backward() through torch.autograd (the engine's region is ONE
     autograd node), torch.optim.Adam.step() and loss.item() -- eager launches, no flat arena, no captured graph
@@ -950,11 +1003,13 @@ def run_unchanged_caller(kind, args, dev, steps, warmup=3, autograph=False):
             def marked():
                 torch.cuda._sleep(1)
                 return step()
-            elapsed, _ = timed(marked, steps, 1, dev)
+            elapsed, loss = timed(marked, steps, 1, dev)
             torch.cuda._sleep(1)
             torch.cuda.synchronize()
         else:
-            elapsed, _ = timed(step, steps, 1, dev)
+            elapsed, loss = timed(step, steps, 1, dev)
+        if dump:
+            dump_outputs(dump, leg_outputs(kind, model, opt, loss))
         return dict(value=n * steps / elapsed, ms_per_step=elapsed * 1e3 / steps, steps=steps, warmup=warmup, settle_steps=0, final_loss=last[0], batch_per_gpu=n,
                     height=h, width=w, autograph=engine.autograph_stats() if autograph else None,
                     launch_mode=("torch.autograd + torch.optim.Adam + loss.item() per step; the model's forward region captured and replayed (engine.set_autograph)"
@@ -1031,7 +1086,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--settle-seconds", type=float, default=2.0, help="untimed replays before the timed region (clock settling)")
+    ap.add_argument("--settle-seconds", type=float, default=None, help="untimed replays before the timed region (clock settling); default 2 "
+                                                                         "with --full, 0 otherwise (a time-bound count of steps would make "
+                                                                         "--dump-outputs differ from run to run)")
     ap.add_argument("--batch", type=int, default=8, help="RC-Net images per GPU and step (BASELINE configs[1]: 8)")
     ap.add_argument("--config3", action="store_true", help="BASELINE configs[3]: global batch 32 over the ranks (4 images per rank on 8 GPUs)")
     ap.add_argument("--dtype", default=os.environ.get("RIDERS_BENCH_DTYPE", "bf16"), choices=["fp32", "bf16", "fp16"],
@@ -1075,7 +1132,19 @@ def main():
     ap.add_argument("--detail", default=None, help="write a per-launch-shape timing table to this file")
     ap.add_argument("--timer-repeat", type=int, default=5, help="idempotent launches issued this many times per HIP-event pair in the instrumented "
                                                                 "steps (1 under rocprofv3, so that its launch counts per step are the real ones)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: the stages timed on their own, instrumented steps and rooflines, profiler "
+                         "children, the fp32 / configs[4] / unchanged-caller legs, val_abs_rel and the CPU baseline; the complete record goes to "
+                         "--full-json.  Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): per stage the loss, the "
+                         "updated parameters, their gradients and the BatchNorm buffers; arrays above %d elements as a fixed seeded sample "
+                         "(<name>_sample.npy)" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.settle_seconds is None:
+        args.settle_seconds = 2.0 if args.full else 0.0
+    if not args.full and (args.detail or args.save_kstats):
+        ap.error("--detail and --save-kstats come from the instrumented steps: add --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -1135,12 +1204,15 @@ def main():
         engine.apply_opts(args.opts)
     rc = sml = None
     legs, caller = {}, None
+    dump = args.dump_outputs if rank == 0 else None
     if args.workload == "chain":
-        head, rc, sml = run_chain(args, dev, world, rank, args.steps, args.warmup)
+        head, rc, sml = run_chain(args, dev, world, rank, args.steps, args.warmup, dump=dump)
     elif args.workload.startswith("caller"):
-        head = run_unchanged_caller("sml" if args.workload.endswith("sml") else "rcnet", args, dev, args.steps, min(args.warmup, 3), autograph=args.autograph)
+        head = run_unchanged_caller("sml" if args.workload.endswith("sml") else "rcnet", args, dev, args.steps, min(args.warmup, 3), autograph=args.autograph,
+                                    dump=dump)
     else:
-        head = run_workload(args.workload, args, dev, world, rank, args.steps, args.warmup, prof_children=(world == 1 and not args.no_children and not args.eager))
+        head = run_workload(args.workload, args, dev, world, rank, args.steps, args.warmup, prof_children=(world == 1 and not args.no_children and not args.eager),
+                            dump=dump)
     default_line = args.workload == "chain" and world == 1 and args.dtype == "bf16" and (args.height, args.width, args.batch) == (256, 512, 8) \
         and not args.config3 and not args.force_ddp and not args.eager
     if world > 1:      # every rank ran the same number of settle steps (and therefore of collectives): checked, not assumed
@@ -1149,7 +1221,7 @@ def main():
         lo, hi = mine.clone(), mine.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         assert int(lo) == int(hi), "ranks ran different numbers of settle steps (%d .. %d)" % (int(lo), int(hi))
-    if default_line and not args.no_legs:
+    if default_line and args.full and not args.no_legs:
         # every mode that carries a claim is timed by the same run: the fp32 parity mode (north_star's 1e-3 holds for it) and BASELINE
         # configs[4] (fp16, 512x1024, batch 8 per GPU); shorter legs, same timing method
         sec_steps = max(1, min(args.steps, 60))
@@ -1178,7 +1250,7 @@ def main():
                 caller[kind] = dict(error=repr(ex)[:300])
     if rank == 0:
         cpu = val = None
-        if world == 1 and not args.no_cpu_baseline and args.workload in ("chain", "rcnet"):
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload in ("chain", "rcnet"):
             try:
                 val = val_abs_rel_pair(dev)
             except Exception as ex:      # never lose the bench line to the auxiliary figure
@@ -1187,14 +1259,15 @@ def main():
         full = full_record(args, world, comm, ddp, head, rc, sml, legs, cpu, val, caller)
         line = compact_line(full)
         # the complete record (per-kernel / per-family / per-shape tables, notes, PMC blocks) goes to the --full-json file; stdout carries
-        # ONE line the driver can hold (round 4's 39.8-KB line was not parsed: BENCH_r04.json.parsed = null)
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(args.full_json)), exist_ok=True)
-            with open(args.full_json, "w") as f:
-                json.dump(full, f)
-        except OSError as ex:
-            sys.stderr.write("bench.py: could not write %s: %r\n" % (args.full_json, ex))
-        sys.stderr.write("bench.py: full record (%d bytes) -> %s\n" % (len(json.dumps(full)), args.full_json))
+        # ONE line the driver can hold (round 4's 39.8-KB line was not parsed: BENCH_r04.json.parsed = null); without --full only when asked for
+        if args.full or args.full_json != ap.get_default("full_json"):
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.full_json)), exist_ok=True)
+                with open(args.full_json, "w") as f:
+                    json.dump(full, f)
+            except OSError as ex:
+                sys.stderr.write("bench.py: could not write %s: %r\n" % (args.full_json, ex))
+            sys.stderr.write("bench.py: full record (%d bytes) -> %s\n" % (len(json.dumps(full)), args.full_json))
         sys.stderr.flush()
         try:      # C-level stdout first (RCCL prints its version banner through stdio: buffered, it would otherwise land behind the line at exit)
             import ctypes

@@ -7,7 +7,7 @@ out=$GRAFT_REPO_ROOT/gpurun_out/ab_lib; mkdir -p $out
 for rep in 1 2; do
 for n in "$@"; do
   if [ "$n" = "new" ]; then unset RIDERS_HIP_LIB; else export RIDERS_HIP_LIB=$GRAFT_REPO_ROOT/tools/ab/lib_$n.so; fi
-  timeout 600 python bench.py --gpus 1 --steps 30 --warmup 5 --no-cpu-baseline --no-legs --no-sml --workload $wl --detail $out/${n}_$wl.txt 2>$out/err.log | python -c "
+  timeout 600 python bench.py --gpus 1 --full --steps 30 --warmup 5 --no-cpu-baseline --no-legs --no-sml --workload $wl --detail $out/${n}_$wl.txt 2>$out/err.log | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

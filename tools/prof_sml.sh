@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$1; mkdir -p $out
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o sml -- python3 $root/bench.py --steps 15 --warmup 3 --no-cpu-baseline --workload sml --settle-seconds 0 > $out/bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o sml -- python3 $root/bench.py --full --steps 15 --warmup 3 --no-cpu-baseline --workload sml --settle-seconds 0 > $out/bench.log 2>&1
 cd $root
 tail -n 1 $out/bench.log | cut -c1-400
 python3 - $out <<'PY'
