@@ -553,14 +553,33 @@ int rd_sml_loss_bwd(const float* pred, const float* gt_interp, const float* gt_s
                     const float* dloss, int32_t N, int32_t H, int32_t W, int32_t filter_size, float w_lidar, float w_smooth, float* dpred,
                     void* stream);
 /* the same for the reference's other supervised terms (utils/loss.py:55-100): loss_kind 0 = 'l1', 1 = 'l2' (mse), 2 = 'smoothl1' (beta 1); with
-   w_edge > 0 (needs w_smooth > 0) the saved gradient fields gfx / gfy also carry the edge-matching term (utils/loss.py:241-249), so the backward
-   below differentiates it too.  rd_sml_loss_fwd / _bwd are loss_kind 0. */
+   w_edge > 0 the saved gradient fields gfx / gfy also carry the edge-matching term (utils/loss.py:241-249), so the backward below differentiates
+   it too.  w_edge > 0 with w_smooth == 0 (utils/loss.py:111): the fields carry the edge term alone, per unit of w_edge -- pass w_edge as the
+   backward's w_smooth; info[3] still reports the smoothness value, as the reference does.  rd_sml_loss_fwd / _bwd are loss_kind 0. */
 int rd_sml_loss_fwd_kind(const float* pred, const float* image, const float* gt_interp, const float* gt_sparse, const float* weights, int32_t N,
                          int32_t H, int32_t W, int32_t filter_size, int32_t loss_kind, float w_lidar, float w_smooth, float w_edge, float* gfx,
                          float* gfy, double* partial, float* info, void* stream);
 int rd_sml_loss_bwd_kind(const float* pred, const float* gt_interp, const float* gt_sparse, const float* gfx, const float* gfy, const float* info,
                          const float* dloss, int32_t N, int32_t H, int32_t W, int32_t filter_size, int32_t loss_kind, float w_lidar, float w_smooth,
                          float* dpred, void* stream);
+/* Lower median (0-based rank (n-1)/2, torch.median) of x0 and of x1 over one selection of their n elements: mask_u8[i] != 0 (the memory of a
+   torch bool tensor) or mask_le0[i] <= 0 -- exactly one of the two masks is non-NULL; x1 may be NULL (= x0).  Exact radix selection on the
+   device: no host synchronisation, fixed grids, integer counts (bit-exact, reproducible), capturable in a hipGraph.  scratch: 16-byte aligned,
+   rd_masked_median_bytes(n) bytes, zero-filled by the call itself.  out[4] = median of x0, median of x1, n selected, 1 if a selected value is
+   NaN; a median is NaN for an empty selection and for one that holds a NaN.  n < 2^31. */
+int64_t rd_masked_median_bytes(int64_t n);
+int rd_masked_median(const float* x0, const float* x1, const uint8_t* mask_u8, const float* mask_le0, int64_t n, void* scratch, float* out,
+                     void* stream);
+/* utils/loss.py:65-70, 83-88, 101-106: loss_unsupervised = mean phi(pred[M] / median(pred[M]) - image[M] / median(image[M])) over the mask M (given
+   as for rd_masked_median; train_zju.py:361 invalid_map_gt = gt <= 0), phi by loss_kind as above.  uinfo[8] = loss_unsupervised, m_o, m_I, n, c (selected
+   pixels equal to m_o), dL/dm_o, nan flag, 0; info (may be NULL): info[0] += w_unsup * loss_unsupervised.  An empty mask gives NaN and no gradient.
+   The backward ADDS dloss * w_unsup * d loss_unsupervised / d pred into dpred on the selected pixels (the median's share split evenly over its c
+   ties, as torch does).  scratch: 16-byte aligned, rd_sml_unsup_bytes(n) bytes. */
+int64_t rd_sml_unsup_bytes(int64_t n);
+int rd_sml_unsup_fwd(const float* pred, const float* image, const uint8_t* mask_u8, const float* mask_le0, int64_t n, int32_t loss_kind, float w_unsup,
+                     void* scratch, float* uinfo, float* info, void* stream);
+int rd_sml_unsup_bwd(const float* pred, const float* image, const uint8_t* mask_u8, const float* mask_le0, int64_t n, int32_t loss_kind, float w_unsup,
+                     const float* uinfo, const float* dloss, float* dpred, void* stream);
 /* val_zju.py:200-206 bicubic (A=-0.75, align_corners=False); :212-231 + utils/eval_utils.py metric sums, res = doubles [N][8] */
 int rd_bicubic_resize(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, void* stream);
 int rd_depth_metrics(const float* out, const float* gt, int32_t N, int32_t HW, float min_depth, float max_depth, double* res, void* stream);

@@ -1021,8 +1021,9 @@ int rd_sml_loss_fwd_kind(const float* pred, const float* image, const float* gi,
   if (!pred || !image || !gi || !gs || !gfx || !gfy || !partial || !info) return fail("sml_loss_fwd: null pointer");
   if (fs < 3 || fs > 9 || !(fs & 1)) return fail("sml_loss: filter size must be odd in 3..9");
   if (loss_kind < 0 || loss_kind > 2) return fail("sml_loss: loss_kind must be 0 ('l1'), 1 ('l2') or 2 ('smoothl1')");
-  if (w_edge > 0.f && !(w_smooth > 0.f)) return fail("sml_loss: w_edge > 0 needs w_smoothness > 0 (the gradient fields are stored per unit of w_smoothness)");
-  rd::launch_sml_loss_fwd(pred, image, gi, gs, weights, N, H, W, fs, (w_lidar > 0.f ? 1 : 0) | (loss_kind << 1), w_lidar, w_smooth, w_edge, gfx, gfy, partial, info, S(stream));
+  // w_edge > 0 without w_smooth > 0 (utils/loss.py:111 allows it): flag bit 3, the fields then carry the edge-matching term alone, per unit of w_edge
+  const int edge_only = (w_edge > 0.f && !(w_smooth > 0.f)) ? 8 : 0;
+  rd::launch_sml_loss_fwd(pred, image, gi, gs, weights, N, H, W, fs, (w_lidar > 0.f ? 1 : 0) | (loss_kind << 1) | edge_only, w_lidar, w_smooth, w_edge, gfx, gfy, partial, info, S(stream));
   return done("rd_sml_loss_fwd_kind");
 }
 int rd_sml_loss_bwd_kind(const float* pred, const float* gi, const float* gs, const float* gfx, const float* gfy, const float* info, const float* dloss,
@@ -1031,6 +1032,38 @@ int rd_sml_loss_bwd_kind(const float* pred, const float* gi, const float* gs, co
   if (loss_kind < 0 || loss_kind > 2) return fail("sml_loss: loss_kind must be 0 ('l1'), 1 ('l2') or 2 ('smoothl1')");
   rd::launch_sml_loss_bwd(pred, gi, gs, gfx, gfy, info, dloss, N, H, W, fs, (w_lidar > 0.f ? 1 : 0) | (loss_kind << 1), w_lidar, w_smooth, dpred, S(stream));
   return done("rd_sml_loss_bwd_kind");
+}
+int64_t rd_masked_median_bytes(int64_t n) { return rd::masked_median_bytes(n); }
+static int select_args_ok(const char* what, const void* x0, const void* x1, const void* mask_u8, const void* mask_le0, int64_t n, const void* scratch) {
+  if (!x0 || !x1) return fail("%s: null pointer", what);
+  if ((mask_u8 != nullptr) == (mask_le0 != nullptr)) return fail("%s: exactly one of mask_u8 / mask_le0 must be given", what);
+  if (n < 0 || n >= ((int64_t)1 << 31)) return fail("%s: n must be below 2^31 (32-bit integer counts)", what);
+  if (scratch && (reinterpret_cast<uintptr_t>(scratch) & 15)) return fail("%s: scratch must be 16-byte aligned", what);
+  return 0;
+}
+int rd_masked_median(const float* x0, const float* x1, const uint8_t* mask_u8, const float* mask_le0, int64_t n, void* scratch, float* out, void* stream) {
+  if (!x1) x1 = x0;
+  if (!out || !scratch) return fail("masked_median: null pointer");
+  if (select_args_ok("masked_median", x0, x1, mask_u8, mask_le0, n, scratch)) return -1;
+  rd::launch_masked_median(x0, x1, mask_u8, mask_le0, n, scratch, out, S(stream));
+  return done("rd_masked_median");
+}
+int64_t rd_sml_unsup_bytes(int64_t n) { return rd::sml_unsup_bytes(n); }
+int rd_sml_unsup_fwd(const float* pred, const float* image, const uint8_t* mask_u8, const float* mask_le0, int64_t n, int32_t loss_kind, float w_unsup,
+                     void* scratch, float* uinfo, float* info, void* stream) {
+  if (!uinfo || !scratch) return fail("sml_unsup_fwd: null pointer");
+  if (select_args_ok("sml_unsup_fwd", pred, image, mask_u8, mask_le0, n, scratch)) return -1;
+  if (loss_kind < 0 || loss_kind > 2) return fail("sml_unsup: loss_kind must be 0 ('l1'), 1 ('l2') or 2 ('smoothl1')");
+  rd::launch_sml_unsup_fwd(pred, image, mask_u8, mask_le0, n, loss_kind, w_unsup, scratch, uinfo, info, S(stream));
+  return done("rd_sml_unsup_fwd");
+}
+int rd_sml_unsup_bwd(const float* pred, const float* image, const uint8_t* mask_u8, const float* mask_le0, int64_t n, int32_t loss_kind, float w_unsup,
+                     const float* uinfo, const float* dloss, float* dpred, void* stream) {
+  if (!uinfo || !dloss || !dpred) return fail("sml_unsup_bwd: null pointer");
+  if (select_args_ok("sml_unsup_bwd", pred, image, mask_u8, mask_le0, n, nullptr)) return -1;
+  if (loss_kind < 0 || loss_kind > 2) return fail("sml_unsup: loss_kind must be 0 ('l1'), 1 ('l2') or 2 ('smoothl1')");
+  rd::launch_sml_unsup_bwd(pred, image, mask_u8, mask_le0, n, loss_kind, w_unsup, uinfo, dloss, dpred, S(stream));
+  return done("rd_sml_unsup_bwd");
 }
 int rd_bicubic_resize(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, void* stream) {
   if (!x || !y) return fail("bicubic_resize: null pointer");

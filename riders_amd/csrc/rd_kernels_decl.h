@@ -210,6 +210,11 @@ void launch_outlier_removal(const float* depth, float* partial, float* out, int 
 int sml_loss_rows(int64_t n);
 void launch_sml_loss_fwd(const float* pred, const float* image, const float* gi, const float* gs, const float* weights, int N, int H, int W, int fs, int mask_interp, float w_lidar, float w_smooth, float w_edge, float* gfx, float* gfy, double* partial, float* info, hipStream_t st);
 void launch_sml_loss_bwd(const float* pred, const float* gi, const float* gs, const float* gfx, const float* gfy, const float* info, const float* dloss, int N, int H, int W, int fs, int mask_interp, float w_lidar, float w_smooth, float* dpred, hipStream_t st);
+int64_t masked_median_bytes(int64_t n);
+void launch_masked_median(const float* x0, const float* x1, const unsigned char* mask_u8, const float* mask_le0, int64_t n, void* scratch, float* out, hipStream_t st);
+int64_t sml_unsup_bytes(int64_t n);
+void launch_sml_unsup_fwd(const float* pred, const float* image, const unsigned char* mask_u8, const float* mask_le0, int64_t n, int kind, float w_u, void* scratch, float* uinfo, float* info, hipStream_t st);
+void launch_sml_unsup_bwd(const float* pred, const float* image, const unsigned char* mask_u8, const float* mask_le0, int64_t n, int kind, float w_u, const float* uinfo, const float* dloss, float* dpred, hipStream_t st);
 void launch_bicubic(const float* x, float* y, int N, int H, int W, int OH, int OW, hipStream_t st);
 void launch_depth_metrics(const float* out, const float* gt, int N, int HW, float dmin, float dmax, double* res, hipStream_t st);
 

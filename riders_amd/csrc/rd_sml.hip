@@ -311,7 +311,10 @@ __global__ __launch_bounds__(256) void sml_loss_fwd_kernel(const float* __restri
                                                            float edge_ratio, float* __restrict__ gfx, float* __restrict__ gfy, double* __restrict__ partial) {
   // flags: bit 0 = mask the interpolated ground truth where sparse lidar exists (loss.py:26-33); bits 1-2 = loss_func 0 'l1', 1 'l2', 2 'smoothl1'
   // (utils/loss.py:55-100).  edge_ratio = w_edge / w_smoothness: the gradient fields then carry the edge-matching term too (loss.py:241-249).
+  // bit 3 = w_edge > 0 with w_smoothness == 0 (loss.py:111): the fields carry the edge-matching term ALONE, per unit of w_edge (edge_ratio is 1), and
+  // the backward is given w_edge as its scale
   const int mask_interp = flags & 1, kind = (flags >> 1) & 3;
+  const bool edge_only = (flags & 8) != 0;
   __shared__ double sh[4];
   const int64_t total = (int64_t)N * H * W;
   const int fs = FS ? FS : fs_rt;
@@ -353,7 +356,7 @@ __global__ __launch_bounds__(256) void sml_loss_fwd_kernel(const float* __restri
     float wx = wt * __expf(-fabsf(sdy)), wy = wt * __expf(-fabsf(sdx));  // x-term weighted by the image's y-gradient (loss.py:235-239)
     acc[4] += wx * fabsf(pdx); acc[5] += wy * fabsf(pdy);
     acc[6] += wt * fabsf(fabsf(pdx) - fabsf(idx)); acc[7] += wt * fabsf(fabsf(pdy) - fabsf(idy));
-    float fx = wx * sgn(pdx), fy = wy * sgn(pdy);
+    float fx = edge_only ? 0.f : wx * sgn(pdx), fy = edge_only ? 0.f : wy * sgn(pdy);
     if (edge_ratio != 0.f) {      // d | |p'| - |i'| | / d p' = sgn(|p'| - |i'|) sgn(p'), weighted like the loss term
       fx += edge_ratio * wt * sgn(fabsf(pdx) - fabsf(idx)) * sgn(pdx);
       fy += edge_ratio * wt * sgn(fabsf(pdy) - fabsf(idy)) * sgn(pdy);
@@ -557,7 +560,7 @@ void launch_sml_loss_fwd(const float* pred, const float* image, const float* gi,
                          float* info, hipStream_t st) {
   int64_t n = (int64_t)N * H * W;
   int rows = sml_loss_rows(n);
-  const float edge_ratio = (w_edge > 0.f && w_smooth > 0.f) ? w_edge / w_smooth : 0.f;      // (mask_interp carries the loss kind in bits 1-2: rd_sml_loss_fwd_kind)
+  const float edge_ratio = (mask_interp & 8) ? 1.f : (w_edge > 0.f && w_smooth > 0.f) ? w_edge / w_smooth : 0.f;      // (mask_interp carries the loss kind in bits 1-2: rd_sml_loss_fwd_kind)
 #define RD_LF(F) hipLaunchKernelGGL((sml_loss_fwd_kernel<F>), dim3(rows), dim3(256), 0, st, pred, image, gi, gs, weights, N, H, W, fs, mask_interp, edge_ratio, gfx, gfy, partial)
   if (fs == 7) RD_LF(7); else if (fs == 5) RD_LF(5); else if (fs == 3) RD_LF(3); else RD_LF(0);
 #undef RD_LF

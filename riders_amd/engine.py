@@ -2450,9 +2450,11 @@ def reciprocal(x):
     return out
 
 
-def sml_loss(pred, image, gt_interp, gt_sparse, weights, w_lidar, w_smooth, w_edge, filter_size, loss_kind=0):
-    """utils/loss.py compute_loss on (N,1,H,W) fp32 contiguous tensors -> (info[7] tensor).  loss_kind 0 'l1', 1 'l2', 2 'smoothl1' (:55-100);
-    w_edge > 0 adds the edge-matching term (:241-249) to the loss AND to the saved gradient fields (needs w_smooth > 0)."""
+def sml_loss(pred, image, gt_interp, gt_sparse, weights, w_lidar, w_smooth, w_edge, filter_size, loss_kind=0, mask=None, w_unsup=0.0):
+    """utils/loss.py compute_loss on (N,1,H,W) fp32 contiguous tensors -> (loss, info[7] tensor, uinfo[8] tensor or None).  loss_kind 0 'l1', 1 'l2',
+    2 'smoothl1' (:55-100); w_edge > 0 adds the edge-matching term (:241-249) to the loss AND to the saved gradient fields (per unit of w_smooth,
+    or of w_edge when w_smooth is 0).  w_unsup > 0 adds the unsupervised term (:65-70) over `mask`: a uint8 tensor (non-zero = selected; the memory
+    of a bool tensor) or a float32 map selected where <= 0; its medians come from the on-device radix selection, uinfo[0] is the unweighted term."""
     lib, t, st = L(), tape(), _stream(pred)
     N, _, H, W = pred.shape
     n = pred.numel()
@@ -2462,6 +2464,17 @@ def sml_loss(pred, image, gt_interp, gt_sparse, weights, w_lidar, w_smooth, w_ed
     info = torch.empty(7, dtype=torch.float32, device=pred.device)
     _chk(lib.rd_sml_loss_fwd_kind(_p(pred), _p(image), _p(gt_interp), _p(gt_sparse), _p(weights), N, H, W, filter_size, int(loss_kind), w_lidar, w_smooth,
                                   w_edge, _p(gfx), _p(gfy), _p(partial), _p(info), st), "rd_sml_loss_fwd_kind")
+    w_fields = w_smooth if w_smooth > 0.0 else w_edge      # what the saved fields are stored per unit of
+    uinfo = None
+    if w_unsup > 0.0:
+        if mask is None or mask.numel() != n or not mask.is_contiguous() or mask.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("sml_loss: w_unsup > 0 needs a contiguous uint8 or float32 mask of the prediction's size")
+        # (mask pointers, at call time: the backward closure below holds the TENSOR, like its neighbours, so the mask's storage lives as long as the tape)
+        mask_ptrs = lambda: (_p(mask), None) if mask.dtype == torch.uint8 else (None, _p(mask))  # noqa: E731
+        mu8, mf = mask_ptrs()
+        scratch = torch.empty(lib.rd_sml_unsup_bytes(n), dtype=torch.uint8, device=pred.device)
+        uinfo = torch.empty(8, dtype=torch.float32, device=pred.device)
+        _chk(lib.rd_sml_unsup_fwd(_p(pred), _p(image), mu8, mf, n, int(loss_kind), w_unsup, _p(scratch), _p(uinfo), _p(info), st), "rd_sml_unsup_fwd")
     loss = info[0]
     if t is not None and t.requires(pred):
         t.mark(loss)
@@ -2472,10 +2485,13 @@ def sml_loss(pred, image, gt_interp, gt_sparse, weights, w_lidar, w_smooth, w_ed
                 return
             dp = torch.empty_like(pred)
             _chk(lib.rd_sml_loss_bwd_kind(_p(pred), _p(gt_interp), _p(gt_sparse), _p(gfx), _p(gfy), _p(info), _p(g), N, H, W, filter_size, int(loss_kind),
-                                          w_lidar, w_smooth, _p(dp), st), "rd_sml_loss_bwd_kind")
+                                          w_lidar, w_fields, _p(dp), st), "rd_sml_loss_bwd_kind")
+            if uinfo is not None:
+                mu8, mf = mask_ptrs()
+                _chk(lib.rd_sml_unsup_bwd(_p(pred), _p(image), mu8, mf, n, int(loss_kind), w_unsup, _p(uinfo), _p(g), _p(dp), st), "rd_sml_unsup_bwd")
             t.add_grad(pred, dp)
         t.record(backward)
-    return loss, info
+    return loss, info, uinfo
 
 
 def outlier_removal(depth, kernel_size, threshold):

@@ -14,7 +14,7 @@ from .net_utils import OutlierRemoval
 
 # train_zju.py:429-487
 ZJU_SML_CONFIG = dict(min_pred=0.1, max_pred=255.0, min_depth=0.0, max_depth=100.0, learning_rate=1e-4, loss_func='l1', w_smoothness=0.2,
-                      w_lidar_loss=1.5, w_edge=0.0, sobel_filter_size=7, outlier_removal_kernel_size=3, outlier_removal_threshold=1.5,
+                      w_lidar_loss=1.5, w_edge=0.0, w_unsupervised=0.0, sobel_filter_size=7, outlier_removal_kernel_size=3, outlier_removal_threshold=1.5,
                       scale_bounds=(0.01, 0.3), mean_std=dict(int_depth=(0.729, 0.210), int_scales=(0.404, 0.117)), interp='rcnet', global_alignment='s')
 
 
@@ -106,12 +106,14 @@ def forward_loss(model, batch, cfg=ZJU_SML_CONFIG, outlier=None):
     d_depth = torch.empty_like(d)
     engine._chk(lib.rd_reciprocal(engine._p(d), None, engine._p(d_depth), d.numel(), engine._stream(d)), "rd_reciprocal")
     sml_depth = engine.run_region(lambda p: engine.reciprocal(p), (pred,), [])
+    w_u = cfg.get('w_unsupervised', 0.0)
+    invalid = gt_r if w_u > 0.0 else None      # train_zju.py:361: the mask is gt <= 0 BEFORE outlier removal; the loss kernels apply the rule to the map itself
     if outlier is not None:
         gt_r = outlier.remove_outliers(gt_r)
     loss, info = compute_loss(image=d_depth, output_depth=sml_depth, gt_interp=gt_r, gt_sparse=sgt_r, loss_func=cfg['loss_func'],
                               w_smoothness=cfg['w_smoothness'], sobel_filter_size=cfg['sobel_filter_size'],
                               validity_map_loss_smoothness=None, w_lidar_loss=cfg['w_lidar_loss'], w_edge=cfg['w_edge'],
-                              invalid_map_gt=None, w_unsupervised=0.0)
+                              invalid_map_gt=invalid, w_unsupervised=w_u)
     return loss
 
 
