@@ -13,6 +13,7 @@ import contextlib
 import os
 import ctypes
 import weakref
+from types import SimpleNamespace as _Plan
 
 import torch
 import torch.distributed
@@ -134,7 +135,6 @@ def set_deterministic_roi_pool(flag):
     _state["deterministic_roi_pool"] = bool(flag)
 
 
-
 def set_fused_loftr(flag):
     """Run eligible LoFTR encoder layers (d_model 128, 8 heads, <= 32 tokens) through the fused per-ROI kernels (default on)."""
     _state["fused_loftr"] = bool(flag)
@@ -144,11 +144,9 @@ def fused_loftr():
     return _state["fused_loftr"]
 
 
-
 def set_defer_wgrad(flag):
     """Group the weight gradients of 1x1 / linear layers into one launch at the end of each tape's backward (default on)."""
     _state["defer_wgrad"] = bool(flag)
-
 
 
 def set_compute_dtype(dt):
@@ -300,6 +298,105 @@ def _bn_bwd_recompute(dz, z, y, mean, rstd, scale, shift, partial, coef2, dgam, 
     rc = _tb("bn_backward", 2.0 * nbytes / 3.0, lambda: lib.rd_bn_act_bwd_recompute_phases(*args, 1, st), desc + " [reduce]", kernel=_bn_name(1, C, dt, act, True))
     rc = rc or _tb("bn_finalize", partial.numel() * 4, lambda: lib.rd_bn_act_bwd_recompute_phases(*args, 2, st), "bn bwd finalize C=%d" % C, kernel="bn_bwd_finalize_kernel")
     return rc or _tb("bn_backward", nbytes, lambda: lib.rd_bn_act_bwd_recompute_phases(*args, 4, st), desc + " [apply]", kernel=_bn_name(2, C, dt, act, True))
+
+
+def _affine_act(y, scale, shift, residual, act, slope):
+    """z = act(scale[c] * y + shift[c] + residual) in one pass (scale / shift None: 1 / 0)"""
+    lib, dt = L(), rd_of(y)
+    C = y.shape[-1]
+    pixels = y.numel() // C
+    z = torch.empty_like(y)
+    _chk(_tb("bn_apply", (2 + (residual is not None)) * y.numel() * y.element_size(),
+             lambda: lib.rd_affine_act(_p(y), _p(scale), _p(shift), _p(residual), _p(z), pixels, C, act, slope, dt, _stream(y)),
+             "bn apply+act M=%d C=%d" % (pixels, C), kernel=_bn_name(0, C, dt, act, residual is not None)), "rd_affine_act")
+    return z
+
+
+def _bn_slab(lib, y, stats, residual, lazy=False):
+    """wide layer on a small map in training mode: finalize + apply in one launch (rd_bn_slab.hip) -- not with a residual (a residual in the
+    convolution's epilogue included) and not when the output stays virtual"""
+    C = y.shape[-1]
+    return bool(stats is not None and residual is None and lib.rd_bn_slab_ok(y.numel() // C, C, rd_of(y)) and not lazy)
+
+
+def _bn_forward(y, bn, act, slope, residual, stats, bn_train, slab, lazy=False, timed=True):
+    """BatchNorm (+ residual, + activation) of an NHWC tensor from the statistics rows its producer (or rd_bn_stats) wrote; eval mode: stats None.
+    -> (z, coef); coef rows = (scale, shift, mean, rstd); lazy: finalize only, z is None (LazyAct).  timed = False keeps the finalize launch out
+    of the kernel timer's records (dwconv_block)."""
+    lib, dt, st = L(), rd_of(y), _stream(y)
+    C = y.shape[-1]
+    pixels = y.numel() // C
+    coef = torch.empty((4, C), dtype=torch.float32, device=y.device)
+    if slab:
+        z = torch.empty_like(y)
+        _chk(_bn_finalize_apply(stats, y, bn, coef, z, pixels, C, act, slope, dt, st), "rd_bn_finalize_apply")
+        return z, coef
+    fin = lambda: lib.rd_bn_finalize(_p(stats), 0 if stats is None else stats.shape[0], C, float(pixels),      # noqa: E731
+                                     _p(bn.weight.detach() if bn.weight is not None else None),
+                                     _p(bn.bias.detach() if bn.bias is not None else None), float(bn.eps),
+                                     float(bn.momentum if bn.momentum is not None else 0.1), 1 if bn_train else 0,
+                                     _p(bn.running_mean), _p(bn.running_var), _p(coef[2]), _p(coef[3]), _p(coef[0]), _p(coef[1]), st)
+    _chk(_tb("bn_finalize", 0 if stats is None else stats.numel() * 4, fin, "bn finalize C=%d" % C) if timed else fin(), "rd_bn_finalize")
+    return (None if lazy else _affine_act(y, coef[0], coef[1], residual, act, slope)), coef
+
+
+def _bn_head_backward(t, hg, y, coef, coef2, dgam, dbet, acc, dy, act, slope):
+    """The layer's output feeds the one-channel output convolution and nothing else: its gradient is a function of the nine neighbouring
+    dlogits, recomputed inside the two passes of the BatchNorm backward (pass 1 also sums the head's weight gradient)."""
+    lib, dt, st, es = L(), rd_of(y), _stream(y), y.element_size()
+    N, OH, OW, C = y.shape
+    pixels, b_out, w_h = N * OH * OW, y.numel() * es, hg.weight
+    hrows = lib.rd_bn_head_rows(N, OH, OW)
+    hpart = torch.empty((hrows, 88, 2), dtype=torch.float32, device=y.device)
+    hargs = (_p(hg.dl), _p(y), _p(coef[2]), _p(coef[3]), _p(coef[0]), _p(coef[1]), act, slope, _p(w_h.detach()))
+    _chk(_timed("bn_backward", 2 * hg.flops, lambda: lib.rd_bn_head_bwd_reduce(*hargs, _p(hpart), N, OH, OW, C, dt, st),
+                "bn+head backward M=%d C=%d [sums + head wgrad]" % (pixels, C), b_out + 2 * pixels * es, kernel=_head_name(1, dt, act), idem=True),
+         "rd_bn_head_bwd_reduce")
+    dwh, acch = t.param_grad(w_h) if hg.w_req else (None, 0)
+    _chk(_timed("bn_backward", hg.flops, lambda: lib.rd_bn_head_bwd_apply(*hargs, _p(hpart), hrows, _p(coef2), _p(dgam), _p(dbet), acc, _p(dwh), acch,
+                                                                           _p(dy), N, OH, OW, C, dt, st),
+                "bn+head backward M=%d C=%d [apply + head dgrad]" % (pixels, C), 2 * b_out + 2 * pixels * es, kernel=_head_name(2, dt, act)),
+         "rd_bn_head_bwd_apply")
+
+
+def _bn_backward(t, dz, z, y, coef, bn, act, slope, has_res, need_res, part=None, timed=True):
+    """backward of _bn_forward (training mode): dz -> (dy, the residual's gradient or None), BatchNorm parameter gradients into the tape.  Four forms:
+    a HeadGrad consumed virtually, the sums already taken by the data gradient that wrote dz (`part`, conv_block's bn_src), the recompute
+    form that does not read z, and the general one (a residual, or bn_recompute off; timed = False: untimed, dwconv_block)."""
+    lib, dt, st = L(), rd_of(y), _stream(y)
+    C = y.shape[-1]
+    pixels, b_out = y.numel() // C, y.numel() * y.element_size()
+    scale, shift, mean, rstd = coef[0], coef[1], coef[2], coef[3]
+    coef2 = torch.empty((2, C), dtype=torch.float32, device=y.device)
+    dgam, acc = t.param_grad(bn.weight)
+    dbet, acc2 = t.param_grad(bn.bias)
+    assert acc == acc2
+    dy = torch.empty_like(y)
+    dres = torch.empty_like(y) if need_res else None
+    if isinstance(dz, HeadGrad) and (need_res or not _state["bn_recompute"]):
+        dz = dz.materialize(t)
+    if isinstance(dz, HeadGrad):
+        _bn_head_backward(t, dz, y, coef, coef2, dgam, dbet, acc, dy, act, slope)
+        return dy, dres
+    if part is not None and part[3] is dz and not need_res:
+        # the data gradient that wrote this very dz tensor already summed (g, g * xhat) over it in its epilogue: finalize + apply only
+        lazy_counts["bn_bwd_fused"] += 1
+        _chk(_tb("bn_backward", 3 * b_out,
+                 lambda: lib.rd_bn_act_bwd_from_partial(_p(dz), _p(y), _p(mean), _p(rstd), _p(scale), _p(shift), _p(part[0]), part[1], part[2],
+                                                        _p(coef2), _p(dgam), _p(dbet), acc, _p(dy), pixels, C, act, slope, dt, st),
+                 "bn backward M=%d C=%d [finalize+apply, sums from the dgrad]" % (pixels, C), kernel=_bn_name(2, C, dt, act, True)),
+             "rd_bn_act_bwd_from_partial")
+        return dy, dres
+    partial = torch.empty((lib.rd_bn_bwd_rows(pixels, C), C, 2), dtype=torch.float32, device=y.device)
+    if not has_res and _state["bn_recompute"]:   # z = act(scale*y + shift): the backward recomputes the activation argument from y, z is not read
+        # algorithmic bytes: dz and y read once, dy written once (the two-pass kernels read dz and y twice)
+        _chk(_bn_bwd_recompute(dz, z, y, mean, rstd, scale, shift, partial, coef2, dgam, dbet, acc, dy, dres, pixels, C, act, slope, dt, st,
+                               3 * b_out, "bn backward M=%d C=%d" % (pixels, C)), "rd_bn_act_bwd_recompute")
+        return dy, dres
+    bwd = lambda: lib.rd_bn_act_bwd(_p(dz), _p(z), _p(y), _p(mean), _p(rstd), _p(scale), _p(partial), _p(coef2), _p(dgam),      # noqa: E731
+                                    _p(dbet), acc, _p(dy), _p(dres), pixels, C, act, slope, dt, st)
+    _chk(_tb("bn_backward", (4 + (dres is not None)) * b_out, bwd, "bn backward(res) M=%d C=%d" % (pixels, C)) if timed else bwd(), "rd_bn_act_bwd")
+    return dy, dres
 
 
 # ------------------------------------------------------------------------------------------------- tape
@@ -1218,6 +1315,301 @@ def _conv_head(lz, xk, weight, N, H, W, C, dt, st):
     return logits
 
 
+def _conv_plan(lib, x, x2, weight, bias, stride, pad, up, bn, act, slope, residual, training, out_hw, lazy_out):
+    """conv_block's shape facts and the route decisions that follow from them alone, made once in the forward.  A plain namespace, no tensor in it:
+    the forward stages add `head`, `d` / `fus` / `d_up2` (_conv_input), `res_fused` (_conv_forward) and `slab`; the backward stages only read."""
+    p = _Plan(dt=rd_of(x), st=_stream(x), es=x.element_size(), ve=16 // x.element_size(), stride=stride, act=act, slope=slope)
+    p.N, p.H1, p.W1, p.C1 = x.shape
+    p.C2 = 0 if x2 is None else x2.shape[3]
+    if weight.dim() == 4:
+        p.Cout, p.Cin, p.KH, p.KW = weight.shape
+    else:
+        (p.Cout, p.Cin), p.KH, p.KW = weight.shape, 1, 1
+    assert p.Cin == p.C1 + p.C2, "conv_block: weight expects %d input channels, got %d" % (p.Cin, p.C1 + p.C2)
+    p.pad = pad = p.KH // 2 if pad is None else pad
+    p.Hin, p.Win = (int(up[0]), int(up[1])) if up is not None else (p.H1, p.W1)
+    p.is_up = up is not None and (p.Hin, p.Win) != (p.H1, p.W1)
+    p.OH = (p.Hin + 2 * pad - p.KH) // stride + 1
+    p.OW = (p.Win + 2 * pad - p.KW) // stride + 1
+    if out_hw is not None:  # asymmetric (TF-"SAME") padding: `pad` is the leading pad, the output size is given
+        p.OH, p.OW = int(out_hw[0]), int(out_hw[1])
+    p.use_bn = bn is not None
+    p.bn_train = p.use_bn and (training or not bn.track_running_stats)
+    p.conv_act = ACT_NONE if (p.use_bn or residual is not None) else act
+    # exact-2x nearest up-sampling of one source (UpConv2d at 15x6 -> 30x12 ... 120x50 -> 240x100), and its 3x3 / stride 1 / pad 1 form
+    p.exact2x = p.is_up and p.C2 == 0 and (p.Hin, p.Win) == (2 * p.H1, 2 * p.W1)
+    p.exact2x_3x3 = p.exact2x and p.KH == 3 and p.KW == 3 and stride == 1 and pad == 1
+    # few-channel inputs (the 3-channel image stems) are zero-padded to one 16-byte vector so that forward and weight gradient run on
+    # the vector / MFMA-bf16 kernels instead of the scalar-gather fallbacks (7x7 stem: 0.31 + 0.52 ms per RC-Net step)
+    p.C1_real, p.cin_pad = p.C1, 0
+    if x2 is None and not p.is_up and p.C1 % p.ve != 0 and p.KH * p.KW >= 9 and not lib.rd_conv_fwd_streams(
+            ctypes.byref(_desc(p.dt, p.N, p.Hin, p.Win, p.C1, 0, False, p.H1, p.W1, p.Cout, p.KH, p.KW, stride, pad, 1, p.OH, p.OW, p.conv_act, slope, p.Cout))):
+        # (layers the streaming few-channel kernels take -- SML's 3 -> 3 `first` convolution -- are handed over as they are; an input that
+        # needs a gradient -- the SML backbone's stem behind `first` -- gets it from the un-padded descriptor in _conv_bwd_data)
+        p.C1 = p.cin_pad = (p.C1 + p.ve - 1) // p.ve * p.ve
+    p.lazy = bool(lazy_out and p.use_bn and residual is None and _state["lazy_bn"] >= int(lazy_out) and _state["bn_recompute"] and p.Cout % p.ve == 0)
+    p.pixels = p.N * p.OH * p.OW
+    p.flops = 2.0 * p.pixels * p.Cout * p.KH * p.KW * p.Cin  # algorithmic (2 FLOP per MAC), same count for dgrad / wgrad
+    p.shp = "M=%d Cin=%d Cout=%d k=%d s=%d%s" % (p.pixels, p.Cin, p.Cout, p.KH, stride, " up" if p.is_up else "")
+    # algorithmic HBM bytes of the three convolution launches (every operand moved exactly once)
+    p.b_in = (p.N * p.H1 * p.W1 * p.C1 + (0 if x2 is None else x2.numel())) * p.es
+    p.b_w, p.b_out = weight.numel() * p.es, p.pixels * p.Cout * p.es
+    return p
+
+
+def _conv_input(lib, p, x, lz, bias, residual, out_hw):
+    """The descriptor and the two input-side routes: a virtual input fused into the staging (p.fus) or written now, and the exact-2x layer on its
+    source (p.d_up2).  -> the tensor the forward reads."""
+    p.d = _desc(p.dt, p.N, p.Hin, p.Win, p.C1, p.C2, p.is_up, p.H1, p.W1, p.Cout, p.KH, p.KW, p.stride, p.pad, 1, p.OH, p.OW, p.conv_act, p.slope, p.Cout)
+    p.fus = None
+    if lz is not None:          # virtual input: fused where the kernel this shape is routed to stages whole channel vectors, else z is written now
+        p.fus = lz.fusion()
+        if p.cin_pad or not lib.rd_conv_fusion_ok(ctypes.byref(p.d), ctypes.byref(p.fus)):
+            assert not p.cin_pad
+            p.fus, x = None, lz.materialize()
+    # exact-2x nearest up-sampling + 3x3: per output parity class (a, b) it is a 2x2 convolution of the SOURCE with pre-summed taps.  Where the
+    # library has that form (rd_conv_up2_ok) the forward runs at source resolution with 4 Cout output channels = (class, channel), skips the
+    # structurally zero (tap, class) blocks and stores depth-to-space: 2.25 x fewer MACs, a quarter of the staged pixels.  The backward keeps the
+    # virtual-resolution form (same function; the pre-summed weights are rounded once more in bf16).
+    p.d_up2 = None
+    if (p.exact2x_3x3 and p.conv_act == ACT_NONE and bias is None and lz is None and out_hw is None and residual is None and _state["up2_on_source"]):
+        d_up2 = _desc(p.dt, p.N, p.H1, p.W1, p.C1, 0, False, p.H1, p.W1, 4 * p.Cout, 3, 3, 1, 1, 1, p.H1, p.W1, ACT_NONE, p.slope, p.Cout)
+        d_up2.out_d2s = 1
+        if lib.rd_conv_up2_ok(ctypes.byref(d_up2)):
+            p.d_up2 = d_up2
+    return x
+
+
+def _conv_forward(lib, p, x, x2, weight, bias, residual, use_stats):
+    """The forward launch, one of four routes: residual in the epilogue (decided here: p.res_fused), exact 2x on the source, virtual input fused,
+    plain.  -> (y, the BatchNorm statistics rows its epilogue wrote or None)"""
+    d, st = p.d, p.st
+    wp = packed_weight(weight, 2 if p.d_up2 is not None else 0, p.dt, p.cin_pad)
+    y = torch.empty((p.N, p.OH, p.OW, p.Cout), dtype=x.dtype, device=x.device)
+    stats = None
+    if use_stats:      # (on the source: rows of 4 Cout columns = four rows of Cout)
+        rows = 4 * lib.rd_conv_stats_rows(ctypes.byref(p.d_up2)) if p.d_up2 is not None else lib.rd_conv_stats_rows(ctypes.byref(d))
+        stats = torch.empty((rows, p.Cout, 2), dtype=torch.float32, device=x.device)
+    bias_t = bias.detach() if bias is not None else None
+    nb = p.b_in + p.b_w + p.b_out
+    p.res_fused = bool(residual is not None and not p.use_bn and p.act == ACT_NONE and p.fus is None and residual.shape == y.shape
+                       and residual.dtype == y.dtype and residual.is_contiguous() and _state["fuse_res_add"] and lib.rd_conv_add_ok(ctypes.byref(d)))
+    if p.res_fused:
+        # conv + bias + residual with no BatchNorm and no activation (the residual units of the SML decoder, modules/midas/blocks.py:99-130):
+        # the residual rides in the convolution's epilogue as its addend (rounded once) instead of a separate add pass over y
+        _chk(_timed("conv_gemm", p.flops, lambda: lib.rd_conv_fwd_add(ctypes.byref(d), _p(x), _p(x2), _p(wp), _p(bias_t), _p(residual), _p(y), st),
+                    "fwd " + p.shp + " (+res)", nb + p.b_out,
+                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(d)).decode(), idem=True), "rd_conv_fwd_add")
+    elif p.d_up2 is not None:
+        lazy_counts["up2_fwd"] += 1
+        _chk(_timed("conv_gemm", p.flops * 4.0 / 9.0, lambda: lib.rd_conv_fwd(ctypes.byref(p.d_up2), _p(x), None, _p(wp), None, _p(y), None, _p(stats), st),
+                    "fwd " + p.shp + " (on source)", nb,
+                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(p.d_up2)).decode(), idem=True), "rd_conv_fwd(up2)")
+    elif p.fus is not None:
+        lazy_counts["fwd_fused"] += 1
+        _chk(_timed("conv_gemm", p.flops, lambda: lib.rd_conv_fwd_fused(ctypes.byref(d), ctypes.byref(p.fus), _p(x), _p(x2), _p(wp), _p(bias_t), None,
+                                                                         _p(y), None, _p(stats), st), "fwd " + p.shp + " (bn-in)", nb,
+                    kernel=lambda: lib.rd_conv_fused_kernel_name(ctypes.byref(d), ctypes.byref(p.fus)).decode(), idem=True), "rd_conv_fwd_fused")
+    else:
+        _chk(_timed("conv_gemm", p.flops, lambda: lib.rd_conv_fwd(ctypes.byref(d), _p(x), _p(x2), _p(wp), _p(bias_t), _p(y), None,
+                                                                   _p(stats), st), "fwd " + p.shp, nb,
+                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(d)).decode(), idem=True), "rd_conv_fwd")
+    return y, stats
+
+
+def _conv_epilogue(lib, p, y, stats, bn, residual):
+    """What follows the convolution: BatchNorm finalize (+ apply + activation, unless the output stays virtual), or the residual / activation pass of a
+    layer without BatchNorm.  -> (z or None, coef or None, the LazyAct or None)"""
+    if p.use_bn:
+        p.slab = _bn_slab(lib, y, stats, residual, p.lazy)
+        z, coef = _bn_forward(y, bn, p.act, p.slope, residual, stats, p.bn_train, p.slab, lazy=p.lazy)
+        # a virtual z: the consumer applies (scale, shift, act) while it stages y
+        return z, coef, (LazyAct(y, coef, p.act, p.slope) if p.lazy else None)
+    p.slab = False
+    if residual is not None and not p.res_fused:
+        return _affine_act(y, None, None, residual, p.act, p.slope), None, None
+    return y, None, None
+
+
+def _conv_bwd_act(t, p, s, dz, src):
+    """backward of what _conv_epilogue ran: dz -> (dy, the residual's gradient)"""
+    if p.use_bn:
+        if not p.bn_train:
+            raise NotImplementedError("backward through eval-mode BatchNorm is not supported")
+        return _bn_backward(t, dz, s.z, s.y, s.coef, s.bn, p.act, p.slope, s.residual is not None, p.need_res, src["partial"] if src is not None else None)
+    if isinstance(dz, HeadGrad):
+        dz = dz.materialize(t)
+    dy = dz
+    if p.act != ACT_NONE:
+        dy = torch.empty_like(s.y)
+        _chk(_tb("elementwise", 3 * p.b_out, lambda: L().rd_act_bwd(_p(dz), _p(s.z), _p(dy), dz.numel(), p.act, p.slope, p.dt, p.st), "act bwd"),
+             "rd_act_bwd")
+    return dy, dy
+
+
+def _conv_bwd_bias(t, p, bias, dy):
+    """bias gradient = the column sums of dy"""
+    lib = L()
+    db, acc = t.param_grad(bias)
+    rows = lib.rd_colsum_rows(p.pixels, p.Cout)
+    part = torch.empty((rows, p.Cout, 2), dtype=torch.float32, device=dy.device)
+    if _state["defer_wgrad"]:      # partial rows now, every layer's final sums in one launch at the next stage mark
+        if any(b_ == id(bias) for _, _, b_ in t.colsum):      # a bias used twice: its two sums must not share a launch
+            t.flush_colsum()
+        _chk(lib.rd_colsum_partial(_p(dy), _p(part), p.pixels, p.Cout, p.dt, p.st), "rd_colsum_partial")
+        t.colsum.append((_lib.ColsumItem(part.data_ptr(), db.data_ptr(), rows, p.Cout, acc, 0), part, id(bias)))
+    else:
+        _chk(lib.rd_colsum(_p(dy), _p(part), _p(db), acc, p.pixels, p.Cout, p.dt, p.st), "rd_colsum")
+
+
+def _conv_wgrad_input(lib, p, s):
+    """-> (the weight gradient's x operand, the fusion it is staged with or None): a virtual input stays virtual where the weight-gradient kernel of
+    this shape can apply (scale, shift, act) itself, else z is written now"""
+    if p.fus is None:
+        return s.x, None
+    if _state["defer_wgrad"] and not (p.KH == 1 and p.KW == 1) and lib.rd_conv_wgrad_fusion_ok(ctypes.byref(p.d), ctypes.byref(p.fus)):
+        return s.x, p.fus
+    return s.lz.materialize(), None
+
+
+def _conv_bwd_weight(t, p, s, x, wfus, dy):
+    """weight gradient of `x` (_conv_wgrad_input) and dy: deferred 1x1, streaming un-padded, padded + unpad, partial (fused), direct"""
+    lib, d, st, weight, x2 = L(), p.d, p.st, s.weight, s.x2
+    if p.KH == 1 and p.KW == 1 and p.stride == 1 and not p.is_up and _state["defer_wgrad"] and p.C1 % p.ve == 0 and p.Cout % p.ve == 0 \
+            and (p.C2 == 0 or (p.C1 % 64 == 0 and p.C2 % p.ve == 0)):
+        t.deferred.append(dict(x=x, x2=x2, dy=dy, weight=weight, M=p.pixels, C1=p.C1, C2=p.C2, Cin=p.Cin, Cout=p.Cout, flops=p.flops))
+        return
+    dw, acc = t.param_grad(weight)
+    ws = torch.empty(lib.rd_conv_wgrad_workspace_bytes(ctypes.byref(d)) // 4, dtype=torch.float32, device=x.device)
+    nb, desc = p.b_in + p.b_out + weight.numel() * 4, "wgrad " + p.shp
+    d_real = _desc(p.dt, p.N, p.Hin, p.Win, p.C1_real, 0, False, p.Hin, p.Win, p.Cout, p.KH, p.KW, p.stride, p.pad, 1, p.OH, p.OW, p.conv_act, p.slope,
+                   p.Cout) if p.cin_pad else None
+    if p.cin_pad and lib.rd_conv_wgrad_streams(ctypes.byref(d_real)):
+        # few channels, millions of pixels: the streaming weight-gradient kernel reads the un-padded tensor directly
+        ws = torch.empty(lib.rd_conv_wgrad_workspace_bytes(ctypes.byref(d_real)) // 4, dtype=torch.float32, device=x.device)
+        _chk(_timed("conv_wgrad", p.flops, lambda: lib.rd_conv_wgrad(ctypes.byref(d_real), _p(s.x_real), None, _p(dy), _p(ws), _p(dw), acc, st), desc, nb),
+             "rd_conv_wgrad")
+    elif p.cin_pad:   # gradient w.r.t. the zero-padded weight, then drop the padded input channels
+        dwp = torch.empty((p.Cout, p.cin_pad, p.KH, p.KW), dtype=torch.float32, device=x.device)
+        _chk(_timed("conv_wgrad", p.flops, lambda: lib.rd_conv_wgrad(ctypes.byref(d), _p(x), None, _p(dy), _p(ws), _p(dwp), 0, st), desc, nb), "rd_conv_wgrad")
+        _chk(lib.rd_unpad_weight_grad(_p(dwp), _p(dw), p.Cout, p.C1_real, p.cin_pad, p.KH * p.KW, acc, st), "rd_unpad_weight_grad")
+    elif _state["defer_wgrad"]:      # slabs now, their reduction with every other layer's in one launch at the next stage mark
+        if id(weight) in t.conv_reduce_w:      # a weight used twice: its two reductions must not share a launch
+            t.flush_conv_reduce()
+        item = _lib.WgradReduceItem()
+        if wfus is not None:
+            lazy_counts["wgrad_fused"] += 1
+            _chk(_timed("conv_wgrad", p.flops, lambda: lib.rd_conv_wgrad_partial_fused(ctypes.byref(d), ctypes.byref(wfus), _p(x), _p(x2), _p(dy),
+                                                                                        _p(ws), _p(dw), acc, ctypes.byref(item), st),
+                        desc + " (bn-in)", nb,
+                        kernel=lambda: lib.rd_conv_wgrad_fused_kernel_name(ctypes.byref(d), ctypes.byref(wfus)).decode(), idem=True), "rd_conv_wgrad_partial_fused")
+        else:
+            _chk(_timed("conv_wgrad", p.flops, lambda: lib.rd_conv_wgrad_partial(ctypes.byref(d), _p(x), _p(x2), _p(dy), _p(ws), _p(dw), acc,
+                                                                                  ctypes.byref(item), st),
+                        desc, nb, kernel=lambda: lib.rd_conv_wgrad_kernel_name(ctypes.byref(d)).decode(), idem=True), "rd_conv_wgrad_partial")
+        t.defer_conv_reduce(item, ws, weight)
+    else:
+        _chk(_timed("conv_wgrad", p.flops, lambda: lib.rd_conv_wgrad(ctypes.byref(d), _p(x), _p(x2), _p(dy), _p(ws), _p(dw), acc, st), desc, nb), "rd_conv_wgrad")
+
+
+def _conv_bwd_data(t, p, s, dy):
+    """data gradient: a convolution of dy with the transposed kernels -- of an exact-2x layer on its source or with the 2x2 blocks summed in the
+    epilogue, else at the (virtual) input resolution (_conv_dgrad_full) followed by the nearest-upsample backward"""
+    lib, st, x, xk = L(), p.st, s.x, s.xk
+    wpd = packed_weight(s.weight, 1, p.dt)
+    Cin_d, C1_d = (p.C1_real, p.C1_real) if p.cin_pad else (p.Cin, p.C1)      # the data gradient has the tensor's own channels, not the padded ones
+    dd = _desc(p.dt, p.N, p.OH, p.OW, p.Cout, 0, False, p.OH, p.OW, Cin_d, p.KH, p.KW, 1, p.KH - 1 - p.pad, p.stride, p.Hin, p.Win, ACT_NONE, 0.0, C1_d)
+    if p.exact2x_3x3 and _state["up2_dgrad"]:
+        # the data gradient of the exact-2x layer ON ITS SOURCE: a 3x3 convolution of dy viewed space-to-depth (4 Cout (class, channel) channels
+        # per source pixel) with the transposed per-class kernels; structurally zero K blocks skipped; no 2x2 reduction pass
+        dd2 = _desc(p.dt, p.N, p.H1, p.W1, 4 * p.Cout, 0, False, p.H1, p.W1, p.C1, 3, 3, 1, 1, 1, p.H1, p.W1, ACT_NONE, 0.0, p.C1)
+        dd2.in_s2d = 1
+        if lib.rd_conv_up2_dgrad_ok(ctypes.byref(dd2)):
+            lazy_counts["up2_dgrad"] += 1
+            g1 = torch.empty_like(x)
+            wp3 = packed_weight(s.weight, 3, p.dt)
+            _chk(_timed("conv_gemm", p.flops * 4.0 / 9.0, lambda: lib.rd_conv_fwd(ctypes.byref(dd2), _p(dy), None, _p(wp3), None, _p(g1), None, None, st),
+                        "dgrad " + p.shp + " (on source)", p.b_out + p.b_w + g1.numel() * p.es,
+                        kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd2)).decode(), idem=True), "rd_conv_fwd(dgrad, in_s2d)")
+            t.add_grad(xk, g1)
+            return
+    if p.exact2x and _state["fuse_upsample_bwd"]:
+        # the kernel sums the 2x2 blocks of its output tile and stores the gradient at SOURCE resolution; the full-resolution tensor and the
+        # upsample_nearest_bwd pass over it disappear
+        dd.out_reduce2 = 1
+        dd.out_reduce2 = 1 if lib.rd_conv_out_reduce2_ok(ctypes.byref(dd)) else 0
+        if dd.out_reduce2:
+            g1 = torch.empty_like(x)
+            _chk(_timed("conv_gemm", p.flops, lambda: lib.rd_conv_fwd(ctypes.byref(dd), _p(dy), None, _p(wpd), None, _p(g1), None, None, st),
+                        "dgrad " + p.shp + " (2x2 summed)", p.b_out + p.b_w + g1.numel() * p.es,
+                        kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd)).decode(), idem=True), "rd_conv_fwd(dgrad, out_reduce2)")
+            t.add_grad(xk, g1)
+            return
+    dxv1 = torch.empty((p.N, p.Hin, p.Win, C1_d), dtype=x.dtype, device=x.device)
+    dxv2 = torch.empty((p.N, p.Hin, p.Win, p.C2), dtype=x.dtype, device=x.device) if p.C2 else None
+    if _conv_dgrad_full(t, p, xk, dy, dd, wpd, dxv1, dxv2, Cin_d, C1_d):
+        return      # (the sum with the earlier contribution already replaced it in t.grads)
+    gs = [dxv1, dxv2]
+    for i, src in enumerate((x, s.x2) if p.is_up else ()):      # nearest-upsample backward: the gradients at the sources' own resolution
+        if src is not None:
+            dxv, g = gs[i], torch.empty_like(src)
+            _chk(_tb("elementwise", (dxv.numel() + g.numel()) * p.es,
+                     lambda: lib.rd_upsample_nearest_bwd(_p(dxv), _p(g), p.N, p.H1, p.W1, p.Hin, p.Win, src.shape[3], p.dt, st), "upsample bwd"),
+                 "rd_upsample_nearest_bwd")
+            gs[i] = g
+    t.add_grad(xk, gs[0])
+    t.add_grad(s.x2, gs[1])
+
+
+def _conv_dgrad_full(t, p, xk, dy, dd, wpd, dxv1, dxv2, Cin_d, C1_d):
+    """The data gradient at the input's (virtual) resolution into dxv1 [, dxv2], with up to two riders in its epilogue: the tensor's earlier gradient
+    contribution as the addend, and the BatchNorm-backward sums of the producer.  -> True when dxv1 became xk's gradient on the tape (addend route)."""
+    lib, st = L(), p.st
+    # x already holds a gradient contribution (a skip connection's decoder side, a residual shortcut): the kernel adds it in its
+    # epilogue and the sum replaces it -- no second tensor, no separate add pass
+    cur = t.grads.get(id(xk)) if (p.C2 == 0 and not p.is_up and _state["fuse_grad_add"] and id(xk) in t.req) else None
+    if isinstance(cur, HeadGrad):      # the one-channel head was this tensor's other consumer: its virtual gradient is written out first
+        cur = t.grads[id(xk)] = cur.materialize(t)
+    if cur is not None and not (cur.shape == dxv1.shape and cur.dtype == dxv1.dtype and cur.is_contiguous() and lib.rd_conv_add_ok(ctypes.byref(dd))):
+        cur = None
+    # x is the output of conv -> BatchNorm -> act (materialised or virtual): this launch writes its dz, so its epilogue also sums the
+    # BatchNorm backward's (g, g * xhat) over what it stores -- the producer's backward then skips its reduce pass over (dz, y).  Valid
+    # only if the tensor written here is the final dz (checked by identity in the producer's backward: a later contribution makes a new one).
+    bsrc = t.bn_src.get(id(xk)) if not p.is_up and not p.cin_pad else None
+    bfus = sb = None
+    if isinstance(t.grads.get(id(xk)), HeadGrad):
+        bsrc = None
+    if bsrc is not None and bsrc["C"] == C1_d and id(xk) in t.req and (cur is not None or t.grads.get(id(xk)) is None):
+        bfus = _lib.ConvFusion()
+        cf = bsrc["coef"]
+        bfus.bn_y, bfus.bn_scale, bfus.bn_shift, bfus.bn_mean, bfus.bn_rstd = _p(bsrc["y"]), _p(cf[0]), _p(cf[1]), _p(cf[2]), _p(cf[3])
+        bfus.bn_act, bfus.bn_slope = bsrc["act"], bsrc["slope"]
+        if lib.rd_conv_fusion_ok(ctypes.byref(dd), ctypes.byref(bfus)):
+            nrows = lib.rd_conv_stats_rows(ctypes.byref(dd))
+            sb = torch.empty((nrows, Cin_d, 2), dtype=torch.float32, device=dy.device)
+        else:
+            bfus = None
+    b_dx = p.N * p.Hin * p.Win * p.Cin * p.es
+    if bfus is not None:
+        _chk(_timed("conv_gemm", p.flops, lambda: lib.rd_conv_fwd_fused(ctypes.byref(dd), ctypes.byref(bfus), _p(dy), None, _p(wpd), None, _p(cur),
+                                                                         _p(dxv1), _p(dxv2), _p(sb), st),
+                    "dgrad " + p.shp + (" (+grad, bn sums)" if cur is not None else " (bn sums)"),
+                    p.b_out + p.b_w + b_dx + p.N * p.Hin * p.Win * C1_d * (2 if cur is not None else 1) * p.es,
+                    kernel=lambda: lib.rd_conv_fused_kernel_name(ctypes.byref(dd), ctypes.byref(bfus)).decode(), idem=True), "rd_conv_fwd_fused(dgrad)")
+        bsrc["partial"] = (sb, nrows, Cin_d, dxv1)
+    elif cur is not None:
+        _chk(_timed("conv_gemm", p.flops, lambda: lib.rd_conv_fwd_add(ctypes.byref(dd), _p(dy), None, _p(wpd), None, _p(cur), _p(dxv1), st),
+                    "dgrad " + p.shp + " (+grad)", p.b_out + p.b_w + 2 * b_dx,
+                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd)).decode(), idem=True), "rd_conv_fwd_add(dgrad)")
+    else:
+        _chk(_timed("conv_gemm", p.flops, lambda: lib.rd_conv_fwd(ctypes.byref(dd), _p(dy), None, _p(wpd), None, _p(dxv1), _p(dxv2),
+                                                                   None, st), "dgrad " + p.shp, p.b_out + p.b_w + b_dx,
+                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd)).decode(), idem=True), "rd_conv_fwd(dgrad)")
+    if cur is not None:
+        t.grads[id(xk)] = dxv1
+    return cur is not None
+
+
 def conv_block(x, weight, *, x2=None, bias=None, stride=1, pad=None, up=None, bn=None, act=ACT_NONE, slope=0.2,
                residual=None, training=True, out_hw=None, lazy_out=False):
     """act(BN(conv([up(x) | up(x2)], weight) + bias) + residual) on NHWC tensors; records its own backward.
@@ -1227,7 +1619,8 @@ def conv_block(x, weight, *, x2=None, bias=None, stride=1, pad=None, up=None, bn
     bn: a torch.nn.BatchNorm2d used as a parameter container (train: batch stats + running update).
     x may be a LazyAct (the un-materialised output of a BatchNorm-ed conv_block): the kernels apply its scale / shift / activation while
     staging; lazy_out = 1 / 2 returns this layer's output as a LazyAct (callers whose consumers are conv_block / add_act) when the engine's
-    lazy_bn level (set_lazy_bn) is at least that.
+    lazy_bn level (set_lazy_bn) is at least that.  The routes are decided once, in the forward, into a plan (_conv_plan); the forward and the
+    recorded backward are the sequence of stages below.
     """
     lib = L()
     t = tape()
@@ -1235,365 +1628,46 @@ def conv_block(x, weight, *, x2=None, bias=None, stride=1, pad=None, up=None, bn
     lz = x if isinstance(x, LazyAct) else None
     if lz is not None:
         x = lz.y
-    dt = rd_of(x)
-    st = _stream(x)
-    N, H1, W1, C1 = x.shape
-    C2 = 0 if x2 is None else x2.shape[3]
-    if weight.dim() == 4:
-        Cout, Cin, KH, KW = weight.shape
-    else:
-        (Cout, Cin), KH, KW = weight.shape, 1, 1
-    assert Cin == C1 + C2, "conv_block: weight expects %d input channels, got %d" % (Cin, C1 + C2)
-    if pad is None:
-        pad = KH // 2
-    Hin, Win = (int(up[0]), int(up[1])) if up is not None else (H1, W1)
-    is_up = up is not None and (Hin, Win) != (H1, W1)
-    OH = (Hin + 2 * pad - KH) // stride + 1
-    OW = (Win + 2 * pad - KW) // stride + 1
-    if out_hw is not None:  # asymmetric (TF-"SAME") padding: `pad` is the leading pad, the output size is given
-        OH, OW = int(out_hw[0]), int(out_hw[1])
-    use_bn = bn is not None
-    conv_act = ACT_NONE if (use_bn or residual is not None) else act
-    # few-channel inputs (the 3-channel image stems) are zero-padded to one 16-byte vector so that forward and weight gradient run on
-    # the vector / MFMA-bf16 kernels instead of the scalar-gather fallbacks (7x7 stem: 0.31 + 0.52 ms per RC-Net step)
-    ve = 16 // x.element_size()
-    cin_pad = 0
-    if x2 is None and not is_up and C1 % ve != 0 and KH * KW >= 9 and not lib.rd_conv_fwd_streams(
-            ctypes.byref(_desc(dt, N, Hin, Win, C1, 0, False, H1, W1, Cout, KH, KW, stride, pad, 1, OH, OW, conv_act, slope, Cout))):
-        # (layers the streaming few-channel kernels take -- SML's 3 -> 3 `first` convolution -- are handed over as they are; an input that
-        # needs a gradient -- the SML backbone's stem behind `first` -- gets it from the un-padded descriptor below)
-        cin_pad = (C1 + ve - 1) // ve * ve
-        xp = torch.empty((N, H1, W1, cin_pad), dtype=x.dtype, device=x.device)
-        _chk(lib.rd_pad_channels(_p(x), _p(xp), N * H1 * W1, C1, cin_pad, dt, st), "rd_pad_channels")
-        x_real, x, C1_real, C1 = x, xp, C1, cin_pad
-    if (lz is not None and _state["bn_head"] and lz._z is None and KH == 3 and KW == 3 and stride == 1 and pad == 1 and Cout == 1 and x2 is None
-            and not is_up and bias is None and not use_bn and residual is None and act == ACT_NONE and out_hw is None and not cin_pad
-            and weight.dtype == torch.float32 and weight.is_contiguous() and (t is None or t.requires(xk))
-            and lib.rd_bn_head_ok(N, H1, W1, C1, dt)):
-        return _conv_head(lz, xk, weight, N, H1, W1, C1, dt, st)
-    d = _desc(dt, N, Hin, Win, C1, C2, is_up, H1, W1, Cout, KH, KW, stride, pad, 1, OH, OW, conv_act, slope, Cout)
-    fus = None
-    if lz is not None:          # virtual input: fused where the kernel this shape is routed to stages whole channel vectors, else z is written now
-        fus = lz.fusion()
-        if cin_pad or not lib.rd_conv_fusion_ok(ctypes.byref(d), ctypes.byref(fus)):
-            assert not cin_pad
-            fus, x = None, lz.materialize()
-    # exact-2x nearest up-sampling + 3x3 (UpConv2d at 15x6 -> 30x12 ... 120x50 -> 240x100): per output parity class (a, b) it is a 2x2 convolution of
-    # the SOURCE with pre-summed taps.  Where the library has that form (rd_conv_up2_ok) the forward runs at source resolution with 4 Cout output
-    # channels = (class, channel), skips the structurally zero (tap, class) blocks and stores depth-to-space: 2.25 x fewer MACs, a quarter of the
-    # staged pixels.  The backward keeps the virtual-resolution form (same function; the pre-summed weights are rounded once more in bf16).
-    d_up2 = None
-    if (is_up and C2 == 0 and (Hin, Win) == (2 * H1, 2 * W1) and KH == 3 and KW == 3 and stride == 1 and pad == 1 and conv_act == ACT_NONE and bias is None and lz is None
-            and not cin_pad and out_hw is None and residual is None and _state["up2_on_source"]):
-        d_up2 = _desc(dt, N, H1, W1, C1, 0, False, H1, W1, 4 * Cout, 3, 3, 1, 1, 1, H1, W1, ACT_NONE, slope, Cout)
-        d_up2.out_d2s = 1
-        if not lib.rd_conv_up2_ok(ctypes.byref(d_up2)):
-            d_up2 = None
-    wp = packed_weight(weight, 2 if d_up2 is not None else 0, dt, cin_pad)
-    y = torch.empty((N, OH, OW, Cout), dtype=x.dtype, device=x.device)
-    stats = None
-    bn_train = use_bn and (training or not bn.track_running_stats)
-    if bn_train:
-        if d_up2 is not None:      # rows of 4 Cout columns = four rows of Cout
-            stats = torch.empty((4 * lib.rd_conv_stats_rows(ctypes.byref(d_up2)), Cout, 2), dtype=torch.float32, device=x.device)
-        else:
-            rows = lib.rd_conv_stats_rows(ctypes.byref(d))
-            stats = torch.empty((rows, Cout, 2), dtype=torch.float32, device=x.device)
-    flops = 2.0 * N * OH * OW * Cout * KH * KW * Cin  # algorithmic (2 FLOP per MAC), same count for dgrad / wgrad
-    shp = "M=%d Cin=%d Cout=%d k=%d s=%d%s" % (N * OH * OW, Cin, Cout, KH, stride, " up" if is_up else "")
-    bias_t = bias.detach() if bias is not None else None
-    es = x.element_size()   # algorithmic HBM bytes of the three convolution launches (every operand moved exactly once)
-    b_in = (x.numel() + (0 if x2 is None else x2.numel())) * es
-    b_w, b_out = weight.numel() * es, N * OH * OW * Cout * es
-    res_fused = False
-    if (residual is not None and not use_bn and act == ACT_NONE and fus is None and residual.shape == y.shape and residual.dtype == y.dtype
-            and residual.is_contiguous() and _state.get("fuse_res_add", True) and lib.rd_conv_add_ok(ctypes.byref(d))):
-        # conv + bias + residual with no BatchNorm and no activation (the residual units of the SML decoder, modules/midas/blocks.py:99-130):
-        # the residual rides in the convolution's epilogue as its addend (rounded once) instead of a separate add pass over y
-        res_fused = True
-        _chk(_timed("conv_gemm", flops, lambda: lib.rd_conv_fwd_add(ctypes.byref(d), _p(x), _p(x2), _p(wp), _p(bias_t), _p(residual), _p(y), st),
-                    "fwd " + shp + " (+res)", b_in + b_w + 2 * b_out,
-                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(d)).decode(), idem=True), "rd_conv_fwd_add")
-    elif d_up2 is not None:
-        lazy_counts["up2_fwd"] += 1
-        _chk(_timed("conv_gemm", flops * 4.0 / 9.0, lambda: lib.rd_conv_fwd(ctypes.byref(d_up2), _p(x), None, _p(wp), None, _p(y), None, _p(stats), st),
-                    "fwd " + shp + " (on source)", b_in + b_w + b_out,
-                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(d_up2)).decode(), idem=True), "rd_conv_fwd(up2)")
-    elif fus is not None:
-        lazy_counts["fwd_fused"] += 1
-        _chk(_timed("conv_gemm", flops, lambda: lib.rd_conv_fwd_fused(ctypes.byref(d), ctypes.byref(fus), _p(x), _p(x2), _p(wp), _p(bias_t), None,
-                                                                         _p(y), None, _p(stats), st), "fwd " + shp + " (bn-in)", b_in + b_w + b_out,
-                    kernel=lambda: lib.rd_conv_fused_kernel_name(ctypes.byref(d), ctypes.byref(fus)).decode(), idem=True), "rd_conv_fwd_fused")
-    else:
-        _chk(_timed("conv_gemm", flops, lambda: lib.rd_conv_fwd(ctypes.byref(d), _p(x), _p(x2), _p(wp), _p(bias_t), _p(y), None,
-                                                                   _p(stats), st), "fwd " + shp, b_in + b_w + b_out,
-                    kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(d)).decode(), idem=True), "rd_conv_fwd")
-    pixels = N * OH * OW
-    scale = shift = mean = rstd = None
-    slab = bool(use_bn and bn_train and stats is not None and residual is None and not res_fused and lib.rd_bn_slab_ok(pixels, Cout, dt)
-                and not (lazy_out and _state["lazy_bn"] >= int(lazy_out) and _state["bn_recompute"] and Cout % ve == 0))
-    if use_bn:
-        coef = torch.empty((4, Cout), dtype=torch.float32, device=x.device)
-        scale, shift, mean, rstd = coef[0], coef[1], coef[2], coef[3]
-    if slab:      # wide layer on a small map: finalize + apply in one launch (rd_bn_slab.hip)
-        z = torch.empty_like(y)
-        _chk(_bn_finalize_apply(stats, y, bn, coef, z, pixels, Cout, act, slope, dt, st), "rd_bn_finalize_apply")
-    elif use_bn:
-        _chk(_tb("bn_finalize", 0 if stats is None else stats.numel() * 4,
-                 lambda: lib.rd_bn_finalize(_p(stats), 0 if stats is None else stats.shape[0], Cout, float(pixels),
-                                            _p(bn.weight.detach() if bn.weight is not None else None),
-                                            _p(bn.bias.detach() if bn.bias is not None else None), float(bn.eps),
-                                            float(bn.momentum if bn.momentum is not None else 0.1), 1 if bn_train else 0,
-                                            _p(bn.running_mean), _p(bn.running_var), _p(mean), _p(rstd), _p(scale), _p(shift), st),
-                 "bn finalize C=%d" % Cout), "rd_bn_finalize")
-    lazy = None
-    if lazy_out and use_bn and residual is None and _state["lazy_bn"] >= int(lazy_out) and _state["bn_recompute"] and Cout % ve == 0:
-        z = None
-        lazy = LazyAct(y, coef, act, slope)      # z stays virtual: the consumer applies (scale, shift, act) while it stages y
-    elif res_fused:
-        z = y
-    elif slab:
-        pass
-    elif use_bn or residual is not None:
-        z = torch.empty_like(y)
-        _chk(_tb("bn_apply", (2 + (residual is not None)) * b_out,
-                 lambda: lib.rd_affine_act(_p(y), _p(scale), _p(shift), _p(residual), _p(z), pixels, Cout, act, slope, dt, st),
-                 "bn apply+act M=%d C=%d" % (pixels, Cout), kernel=_bn_name(0, Cout, dt, act, residual is not None)), "rd_affine_act")
-    else:
-        z = y
+    p = _conv_plan(lib, x, x2, weight, bias, stride, pad, up, bn, act, slope, residual, training, out_hw, lazy_out)
+    x_real = None
+    if p.cin_pad:
+        x_real, x = x, torch.empty((p.N, p.H1, p.W1, p.cin_pad), dtype=x.dtype, device=x.device)
+        _chk(lib.rd_pad_channels(_p(x_real), _p(x), p.N * p.H1 * p.W1, p.C1_real, p.cin_pad, p.dt, p.st), "rd_pad_channels")
+    p.head = bool(lz is not None and _state["bn_head"] and lz._z is None and p.KH == 3 and p.KW == 3 and stride == 1 and p.pad == 1 and p.Cout == 1 and x2 is None
+                  and not p.is_up and bias is None and not p.use_bn and residual is None and act == ACT_NONE and out_hw is None and not p.cin_pad
+                  and weight.dtype == torch.float32 and weight.is_contiguous() and (t is None or t.requires(xk))
+                  and lib.rd_bn_head_ok(p.N, p.H1, p.W1, p.C1, p.dt))
+    if p.head:
+        return _conv_head(lz, xk, weight, p.N, p.H1, p.W1, p.C1, p.dt, p.st)
+    x = _conv_input(lib, p, x, lz, bias, residual, out_hw)
+    y, stats = _conv_forward(lib, p, x, x2, weight, bias, residual, p.bn_train)
+    z, coef, lazy = _conv_epilogue(lib, p, y, stats, bn, residual)
     zk = lazy if lazy is not None else z      # what the caller receives = the tape key of this layer's output
     if t is None:
         return zk
-
-    need_in = t.requires(xk, x2)
-    need_res = t.requires(residual)
-    w_req = weight.requires_grad
-    if not (need_in or need_res or w_req or (use_bn and bn.weight is not None and bn.weight.requires_grad)):
+    p.need_in, p.need_res, p.w_req = t.requires(xk, x2), t.requires(residual), weight.requires_grad
+    if not (p.need_in or p.need_res or p.w_req or (p.use_bn and bn.weight is not None and bn.weight.requires_grad)):
         return zk
     t.mark(zk)
-    if use_bn and bn_train and residual is None and _state["bn_recompute"] and _state["bn_bwd_fused"] and Cout % ve == 0:
-        t.bn_src[id(zk)] = dict(y=y, coef=coef, act=act, slope=slope, C=Cout, partial=None)
+    if p.bn_train and residual is None and _state["bn_recompute"] and _state["bn_bwd_fused"] and p.Cout % p.ve == 0:
+        t.bn_src[id(zk)] = dict(y=y, coef=coef, act=act, slope=slope, C=p.Cout, partial=None)
+    s = _Plan(x=x, x_real=x_real, x2=x2, xk=xk, lz=lz, y=y, z=z, coef=coef, bn=bn, weight=weight, residual=residual)      # what the backward keeps alive
 
     def backward():
-        nonlocal x
         dz = t.pop_grad(zk)
         src = t.bn_src.pop(id(zk), None)
         if dz is None:
             return
-        dres = None
-        if use_bn:
-            if not bn_train:
-                raise NotImplementedError("backward through eval-mode BatchNorm is not supported")
-            coef2 = torch.empty((2, Cout), dtype=torch.float32, device=x.device)
-            dgam, acc = t.param_grad(bn.weight)
-            dbet, acc2 = t.param_grad(bn.bias)
-            assert acc == acc2
-            dy = torch.empty_like(y)
-            dres = torch.empty_like(y) if need_res else None
-            part = src["partial"] if src is not None else None
-            if isinstance(dz, HeadGrad) and (need_res or not _state["bn_recompute"]):
-                dz = dz.materialize(t)
-            if isinstance(dz, HeadGrad):
-                # this layer's output feeds the one-channel output convolution and nothing else: its gradient is a function of the nine
-                # neighbouring dlogits, recomputed inside the two passes of the BatchNorm backward (pass 1 also sums the head's weight gradient)
-                hg, w_h = dz, dz.weight
-                hrows = lib.rd_bn_head_rows(N, OH, OW)
-                hpart = torch.empty((hrows, 88, 2), dtype=torch.float32, device=x.device)
-                hargs = (_p(hg.dl), _p(y), _p(mean), _p(rstd), _p(scale), _p(shift), act, slope, _p(w_h.detach()))
-                _chk(_timed("bn_backward", 2 * hg.flops, lambda: lib.rd_bn_head_bwd_reduce(*hargs, _p(hpart), N, OH, OW, Cout, dt, st),
-                            "bn+head backward M=%d C=%d [sums + head wgrad]" % (pixels, Cout), b_out + 2 * pixels * es, kernel=_head_name(1, dt, act), idem=True),
-                     "rd_bn_head_bwd_reduce")
-                dwh, acch = t.param_grad(w_h) if hg.w_req else (None, 0)
-                _chk(_timed("bn_backward", hg.flops, lambda: lib.rd_bn_head_bwd_apply(*hargs, _p(hpart), hrows, _p(coef2), _p(dgam), _p(dbet), acc, _p(dwh), acch,
-                                                                                       _p(dy), N, OH, OW, Cout, dt, st),
-                            "bn+head backward M=%d C=%d [apply + head dgrad]" % (pixels, Cout), 2 * b_out + 2 * pixels * es, kernel=_head_name(2, dt, act)),
-                     "rd_bn_head_bwd_apply")
-                partial = None
-            elif part is not None and part[3] is dz and not need_res:
-                # the data gradient that wrote this very dz tensor already summed (g, g * xhat) over it in its epilogue: finalize + apply only
-                lazy_counts["bn_bwd_fused"] += 1
-                _chk(_tb("bn_backward", 3 * b_out,
-                         lambda: lib.rd_bn_act_bwd_from_partial(_p(dz), _p(y), _p(mean), _p(rstd), _p(scale), _p(shift), _p(part[0]), part[1], part[2],
-                                                                _p(coef2), _p(dgam), _p(dbet), acc, _p(dy), pixels, Cout, act, slope, dt, st),
-                         "bn backward M=%d C=%d [finalize+apply, sums from the dgrad]" % (pixels, Cout), kernel=_bn_name(2, Cout, dt, act, True)),
-                     "rd_bn_act_bwd_from_partial")
-                partial = None
-            else:
-                rows = lib.rd_bn_bwd_rows(pixels, Cout)
-                partial = torch.empty((rows, Cout, 2), dtype=torch.float32, device=x.device)
-            if partial is None:
-                pass
-            elif residual is None and _state["bn_recompute"]:   # z = act(scale*y + shift): the backward recomputes the activation argument from y, z is not read
-                # algorithmic bytes: dz and y read once, dy written once (the two-pass kernels read dz and y twice)
-                _chk(_bn_bwd_recompute(dz, z, y, mean, rstd, scale, shift, partial, coef2, dgam, dbet, acc, dy, dres, pixels, Cout, act, slope, dt, st,
-                                       3 * b_out, "bn backward M=%d C=%d" % (pixels, Cout)), "rd_bn_act_bwd_recompute")
-            else:
-                _chk(_tb("bn_backward", (4 + (dres is not None)) * b_out,
-                         lambda: lib.rd_bn_act_bwd(_p(dz), _p(z), _p(y), _p(mean), _p(rstd), _p(scale), _p(partial), _p(coef2), _p(dgam),
-                                                   _p(dbet), acc, _p(dy), _p(dres), pixels, Cout, act, slope, dt, st),
-                         "bn backward(res) M=%d C=%d" % (pixels, Cout)), "rd_bn_act_bwd")
-        else:
-            if isinstance(dz, HeadGrad):
-                dz = dz.materialize(t)
-            eff_act = act
-            if eff_act != ACT_NONE:
-                dy = torch.empty_like(y)
-                _chk(_tb("elementwise", 3 * b_out, lambda: lib.rd_act_bwd(_p(dz), _p(z), _p(dy), dz.numel(), eff_act, slope, dt, st), "act bwd"),
-                     "rd_act_bwd")
-            else:
-                dy = dz
-            dres = dy
-        if need_res:
+        dy, dres = _conv_bwd_act(t, p, s, dz, src)
+        if p.need_res:
             t.add_grad(residual, dres)
         if bias is not None and bias.requires_grad:
-            db, acc = t.param_grad(bias)
-            rows = lib.rd_colsum_rows(pixels, Cout)
-            part = torch.empty((rows, Cout, 2), dtype=torch.float32, device=x.device)
-            if _state["defer_wgrad"]:      # partial rows now, every layer's final sums in one launch at the next stage mark
-                if any(b_ == id(bias) for _, _, b_ in t.colsum):      # a bias used twice: its two sums must not share a launch
-                    t.flush_colsum()
-                _chk(lib.rd_colsum_partial(_p(dy), _p(part), pixels, Cout, dt, st), "rd_colsum_partial")
-                t.colsum.append((_lib.ColsumItem(part.data_ptr(), db.data_ptr(), rows, Cout, acc, 0), part, id(bias)))
-            else:
-                _chk(lib.rd_colsum(_p(dy), _p(part), _p(db), acc, pixels, Cout, dt, st), "rd_colsum")
-        ve = 16 // es
-        wfus = None
-        if w_req and fus is not None:       # the weight gradient's x operand is the virtual z too: fused where its kernel can, else z is written now
-            if _state["defer_wgrad"] and not (KH == 1 and KW == 1) and lib.rd_conv_wgrad_fusion_ok(ctypes.byref(d), ctypes.byref(fus)):
-                wfus = fus
-            else:
-                x = lz.materialize()
-        if w_req and KH == 1 and KW == 1 and stride == 1 and not is_up and _state["defer_wgrad"] and C1 % ve == 0 and Cout % ve == 0 \
-                and (C2 == 0 or (C1 % 64 == 0 and C2 % ve == 0)):
-            t.deferred.append(dict(x=x, x2=x2, dy=dy, weight=weight, M=pixels, C1=C1, C2=C2, Cin=Cin, Cout=Cout, flops=flops))
-        elif w_req:
-            dw, acc = t.param_grad(weight)
-            ws = torch.empty(lib.rd_conv_wgrad_workspace_bytes(ctypes.byref(d)) // 4, dtype=torch.float32, device=x.device)
-            d_real = _desc(dt, N, Hin, Win, C1_real, 0, False, Hin, Win, Cout, KH, KW, stride, pad, 1, OH, OW, conv_act, slope, Cout) if cin_pad else None
-            if cin_pad and lib.rd_conv_wgrad_streams(ctypes.byref(d_real)):
-                # few channels, millions of pixels: the streaming weight-gradient kernel reads the un-padded tensor directly
-                ws = torch.empty(lib.rd_conv_wgrad_workspace_bytes(ctypes.byref(d_real)) // 4, dtype=torch.float32, device=x.device)
-                _chk(_timed("conv_wgrad", flops, lambda: lib.rd_conv_wgrad(ctypes.byref(d_real), _p(x_real), None, _p(dy), _p(ws), _p(dw), acc, st),
-                            "wgrad " + shp, b_in + b_out + weight.numel() * 4), "rd_conv_wgrad")
-            elif cin_pad:   # gradient w.r.t. the zero-padded weight, then drop the padded input channels
-                dwp = torch.empty((Cout, cin_pad, KH, KW), dtype=torch.float32, device=x.device)
-                _chk(_timed("conv_wgrad", flops, lambda: lib.rd_conv_wgrad(ctypes.byref(d), _p(x), None, _p(dy), _p(ws), _p(dwp), 0, st),
-                            "wgrad " + shp, b_in + b_out + weight.numel() * 4), "rd_conv_wgrad")
-                _chk(lib.rd_unpad_weight_grad(_p(dwp), _p(dw), Cout, C1_real, cin_pad, KH * KW, acc, st), "rd_unpad_weight_grad")
-            elif _state["defer_wgrad"]:      # slabs now, their reduction with every other layer's in one launch at the next stage mark
-                if id(weight) in t.conv_reduce_w:      # a weight used twice: its two reductions must not share a launch
-                    t.flush_conv_reduce()
-                item = _lib.WgradReduceItem()
-                st_w = st
-                if wfus is not None:
-                    lazy_counts["wgrad_fused"] += 1
-                    _chk(_timed("conv_wgrad", flops, lambda: lib.rd_conv_wgrad_partial_fused(ctypes.byref(d), ctypes.byref(wfus), _p(x), _p(x2), _p(dy),
-                                                                                                _p(ws), _p(dw), acc, ctypes.byref(item), st_w),
-                                "wgrad " + shp + " (bn-in)", b_in + b_out + weight.numel() * 4,
-                                kernel=lambda: lib.rd_conv_wgrad_fused_kernel_name(ctypes.byref(d), ctypes.byref(wfus)).decode(), idem=True), "rd_conv_wgrad_partial_fused")
-                else:
-                    _chk(_timed("conv_wgrad", flops, lambda: lib.rd_conv_wgrad_partial(ctypes.byref(d), _p(x), _p(x2), _p(dy), _p(ws), _p(dw), acc,
-                                                                                          ctypes.byref(item), st_w),
-                                "wgrad " + shp, b_in + b_out + weight.numel() * 4,
-                                kernel=lambda: lib.rd_conv_wgrad_kernel_name(ctypes.byref(d)).decode(), idem=True), "rd_conv_wgrad_partial")
-                t.defer_conv_reduce(item, ws, weight)
-            else:
-                _chk(_timed("conv_wgrad", flops, lambda: lib.rd_conv_wgrad(ctypes.byref(d), _p(x), _p(x2), _p(dy), _p(ws), _p(dw), acc, st),
-                            "wgrad " + shp, b_in + b_out + weight.numel() * 4), "rd_conv_wgrad")
-        if need_in:
-            wpd = packed_weight(weight, 1, dt)
-            Cin_d, C1_d = (C1_real, C1_real) if cin_pad else (Cin, C1)      # the data gradient has the tensor's own channels, not the padded ones
-            dd = _desc(dt, N, OH, OW, Cout, 0, False, OH, OW, Cin_d, KH, KW, 1, KH - 1 - pad, stride, Hin, Win, ACT_NONE, 0.0, C1_d)
-            # exact 2x nearest up-sampling (UpConv2d at 120x50 -> 240x100 ...): the kernel sums the 2x2 blocks of its output tile and stores the
-            # gradient at SOURCE resolution; the full-resolution tensor and the upsample_nearest_bwd pass over it disappear
-            if (is_up and C2 == 0 and (Hin, Win) == (2 * H1, 2 * W1) and KH == 3 and KW == 3 and stride == 1 and pad == 1 and not cin_pad
-                    and _state["up2_dgrad"]):
-                # the data gradient of the exact-2x layer ON ITS SOURCE: a 3x3 convolution of dy viewed space-to-depth (4 Cout (class, channel) channels
-                # per source pixel) with the transposed per-class kernels; structurally zero K blocks skipped; no 2x2 reduction pass
-                dd2 = _desc(dt, N, H1, W1, 4 * Cout, 0, False, H1, W1, C1, 3, 3, 1, 1, 1, H1, W1, ACT_NONE, 0.0, C1)
-                dd2.in_s2d = 1
-                if lib.rd_conv_up2_dgrad_ok(ctypes.byref(dd2)):
-                    lazy_counts["up2_dgrad"] += 1
-                    g1 = torch.empty_like(x)
-                    wp3 = packed_weight(weight, 3, dt)
-                    _chk(_timed("conv_gemm", flops * 4.0 / 9.0, lambda: lib.rd_conv_fwd(ctypes.byref(dd2), _p(dy), None, _p(wp3), None, _p(g1), None, None, st),
-                                "dgrad " + shp + " (on source)", b_out + b_w + g1.numel() * es,
-                                kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd2)).decode(), idem=True), "rd_conv_fwd(dgrad, in_s2d)")
-                    t.add_grad(xk, g1)
-                    return
-            fused_up = False
-            if is_up and C2 == 0 and (Hin, Win) == (2 * H1, 2 * W1) and _state.get("fuse_upsample_bwd", True):
-                dd.out_reduce2 = 1
-                fused_up = bool(lib.rd_conv_out_reduce2_ok(ctypes.byref(dd)))
-                dd.out_reduce2 = 1 if fused_up else 0
-            if fused_up:
-                g1 = torch.empty_like(x)
-                _chk(_timed("conv_gemm", flops, lambda: lib.rd_conv_fwd(ctypes.byref(dd), _p(dy), None, _p(wpd), None, _p(g1), None, None, st),
-                            "dgrad " + shp + " (2x2 summed)", b_out + b_w + g1.numel() * es,
-                            kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd)).decode(), idem=True), "rd_conv_fwd(dgrad, out_reduce2)")
-                t.add_grad(xk, g1)
-                return
-            dxv1 = torch.empty((N, Hin, Win, C1_d), dtype=x.dtype, device=x.device)
-            dxv2 = torch.empty((N, Hin, Win, C2), dtype=x.dtype, device=x.device) if C2 else None
-            # x already holds a gradient contribution (a skip connection's decoder side, a residual shortcut): the kernel adds it in its
-            # epilogue and the sum replaces it -- no second tensor, no separate add pass
-            cur = t.grads.get(id(xk)) if (C2 == 0 and not is_up and _state.get("fuse_grad_add", True) and id(xk) in t.req) else None
-            if isinstance(cur, HeadGrad):      # the one-channel head was this tensor's other consumer: its virtual gradient is written out first
-                cur = t.grads[id(xk)] = cur.materialize(t)
-            if cur is not None and not (cur.shape == dxv1.shape and cur.dtype == dxv1.dtype and cur.is_contiguous() and lib.rd_conv_add_ok(ctypes.byref(dd))):
-                cur = None
-            # x is the output of conv -> BatchNorm -> act (materialised or virtual): this launch writes its dz, so its epilogue also sums the
-            # BatchNorm backward's (g, g * xhat) over what it stores -- the producer's backward then skips its reduce pass over (dz, y).  Valid
-            # only if the tensor written here is the final dz (checked by identity in the producer's backward: a later contribution makes a new one).
-            bsrc = t.bn_src.get(id(xk)) if not is_up and not cin_pad else None
-            bfus = sb = None
-            if isinstance(t.grads.get(id(xk)), HeadGrad):
-                bsrc = None
-            if bsrc is not None and bsrc["C"] == C1_d and id(xk) in t.req and (cur is not None or t.grads.get(id(xk)) is None):
-                bfus = _lib.ConvFusion()
-                cf = bsrc["coef"]
-                bfus.bn_y, bfus.bn_scale, bfus.bn_shift, bfus.bn_mean, bfus.bn_rstd = _p(bsrc["y"]), _p(cf[0]), _p(cf[1]), _p(cf[2]), _p(cf[3])
-                bfus.bn_act, bfus.bn_slope = bsrc["act"], bsrc["slope"]
-                if lib.rd_conv_fusion_ok(ctypes.byref(dd), ctypes.byref(bfus)):
-                    nrows = lib.rd_conv_stats_rows(ctypes.byref(dd))
-                    sb = torch.empty((nrows, Cin_d, 2), dtype=torch.float32, device=x.device)
-                else:
-                    bfus = None
-            if bfus is not None:
-                _chk(_timed("conv_gemm", flops, lambda: lib.rd_conv_fwd_fused(ctypes.byref(dd), ctypes.byref(bfus), _p(dy), None, _p(wpd), None, _p(cur),
-                                                                                 _p(dxv1), _p(dxv2), _p(sb), st),
-                            "dgrad " + shp + (" (+grad, bn sums)" if cur is not None else " (bn sums)"),
-                            b_out + b_w + (N * Hin * Win * Cin + N * Hin * Win * C1_d * (2 if cur is not None else 1)) * es,
-                            kernel=lambda: lib.rd_conv_fused_kernel_name(ctypes.byref(dd), ctypes.byref(bfus)).decode(), idem=True), "rd_conv_fwd_fused(dgrad)")
-                bsrc["partial"] = (sb, nrows, Cin_d, dxv1)
-                if cur is not None:
-                    t.grads[id(xk)] = dxv1
-                    return
-            elif cur is not None:
-                _chk(_timed("conv_gemm", flops, lambda: lib.rd_conv_fwd_add(ctypes.byref(dd), _p(dy), None, _p(wpd), None, _p(cur), _p(dxv1), st),
-                            "dgrad " + shp + " (+grad)", b_out + b_w + 2 * N * Hin * Win * Cin * es,
-                            kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd)).decode(), idem=True), "rd_conv_fwd_add(dgrad)")
-                t.grads[id(xk)] = dxv1
-                return
-            else:
-                _chk(_timed("conv_gemm", flops, lambda: lib.rd_conv_fwd(ctypes.byref(dd), _p(dy), None, _p(wpd), None, _p(dxv1), _p(dxv2),
-                                                                           None, st), "dgrad " + shp, b_out + b_w + N * Hin * Win * Cin * es,
-                            kernel=lambda: lib.rd_conv_fwd_kernel_name(ctypes.byref(dd)).decode(), idem=True), "rd_conv_fwd(dgrad)")
-            if is_up:
-                g1 = torch.empty_like(x)
-                _chk(_tb("elementwise", (dxv1.numel() + g1.numel()) * es,
-                         lambda: lib.rd_upsample_nearest_bwd(_p(dxv1), _p(g1), N, H1, W1, Hin, Win, C1, dt, st), "upsample bwd"),
-                     "rd_upsample_nearest_bwd")
-                g2 = None
-                if C2:
-                    g2 = torch.empty_like(x2)
-                    _chk(_tb("elementwise", (dxv2.numel() + g2.numel()) * es,
-                             lambda: lib.rd_upsample_nearest_bwd(_p(dxv2), _p(g2), N, H1, W1, Hin, Win, C2, dt, st), "upsample bwd"),
-                         "rd_upsample_nearest_bwd")
-            else:
-                g1, g2 = dxv1, dxv2
-            t.add_grad(xk, g1)
-            t.add_grad(x2, g2)
+            _conv_bwd_bias(t, p, bias, dy)
+        if p.w_req:
+            xw, wfus = _conv_wgrad_input(lib, p, s)
+            _conv_bwd_weight(t, p, s, xw, wfus, dy)
+        if p.need_in:
+            _conv_bwd_data(t, p, s, dy)
 
     t.record(backward)
     return zk
@@ -2266,54 +2340,6 @@ def bce_masked(logits, label, valid, pos_weight):
 
 
 # =================================================================================== Scale Map Learner ops
-def _bn_forward(y, bn, act, slope, residual, training, stats=None):
-    """BatchNorm (+residual, +activation) on an NHWC tensor whose producer has no fused statistics epilogue."""
-    lib, dt, st = L(), rd_of(y), _stream(y)
-    C = y.shape[-1]
-    pixels = y.numel() // C
-    bn_train = training or not bn.track_running_stats
-    if bn_train and stats is None:
-        rows = lib.rd_dw_rows(pixels, C)
-        stats = torch.empty((rows, C, 2), dtype=torch.float32, device=y.device)
-        _chk(lib.rd_bn_stats(_p(y), _p(stats), pixels, C, dt, st), "rd_bn_stats")
-    coef = torch.empty((4, C), dtype=torch.float32, device=y.device)
-    if bn_train and residual is None and lib.rd_bn_slab_ok(pixels, C, dt):
-        z = torch.empty_like(y)
-        _chk(_bn_finalize_apply(stats, y, bn, coef, z, pixels, C, act, slope, dt, st), "rd_bn_finalize_apply")
-        return z, coef, bn_train
-    _chk(lib.rd_bn_finalize(_p(stats), 0 if stats is None else stats.shape[0], C, float(pixels), _p(bn.weight.detach()), _p(bn.bias.detach()),
-                            float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.1), 1 if bn_train else 0,
-                            _p(bn.running_mean), _p(bn.running_var), _p(coef[2]), _p(coef[3]), _p(coef[0]), _p(coef[1]), st), "rd_bn_finalize")
-    z = torch.empty_like(y)
-    _chk(_tb("bn_apply", (2 + (residual is not None)) * y.numel() * y.element_size(),
-             lambda: lib.rd_affine_act(_p(y), _p(coef[0]), _p(coef[1]), _p(residual), _p(z), pixels, C, act, slope, dt, st),
-             "bn apply+act M=%d C=%d" % (pixels, C), kernel=_bn_name(0, C, dt, act, residual is not None)), "rd_affine_act")
-    return z, coef, bn_train
-
-
-def _bn_backward(t, dz, z, y, coef, bn, act, slope, want_res):
-    lib, dt, st = L(), rd_of(y), _stream(y)
-    C = y.shape[-1]
-    pixels = y.numel() // C
-    rows = lib.rd_bn_bwd_rows(pixels, C)
-    partial = torch.empty((rows, C, 2), dtype=torch.float32, device=y.device)
-    coef2 = torch.empty((2, C), dtype=torch.float32, device=y.device)
-    dgam, acc = t.param_grad(bn.weight)
-    dbet, _ = t.param_grad(bn.bias)
-    dy = torch.empty_like(y)
-    dres = torch.empty_like(y) if want_res else None
-    if not _state["bn_recompute"]:
-        _chk(lib.rd_bn_act_bwd(_p(dz), _p(z), _p(y), _p(coef[2]), _p(coef[3]), _p(coef[0]), _p(partial), _p(coef2), _p(dgam), _p(dbet), acc,
-                               _p(dy), _p(dres), pixels, C, act, slope, dt, st), "rd_bn_act_bwd")
-        return dy, dres
-    # no residual on this path: the activation argument is recomputed from y (coef[0] = scale, coef[1] = shift), z is not read
-    _chk(_bn_bwd_recompute(dz, z, y, coef[2], coef[3], coef[0], coef[1], partial, coef2, dgam, dbet, acc, dy, dres, pixels, C, act, slope, dt, st,
-                           3 * y.numel() * y.element_size(), "bn backward M=%d C=%d" % (pixels, C)), "rd_bn_act_bwd_recompute")
-    return dy, dres
-
-
-
-
 def dwconv_block(x, weight, *, stride=1, pad=0, out_hw=None, bn=None, act=ACT_NONE, slope=0.0, training=True):
     """act(BN(depthwise_conv(x))) for the EfficientNet-Lite blocks; weight (C,1,k,k) fp32."""
     lib, t, dt, st = L(), tape(), rd_of(x), _stream(x)
@@ -2328,10 +2354,14 @@ def dwconv_block(x, weight, *, stride=1, pad=0, out_hw=None, bn=None, act=ACT_NO
         _chk(lib.rd_dwconv_fwd_stats(_p(x), _p(weight.detach()), _p(y), _p(stats), N, H, W, C, OH, OW, k, stride, pad, dt, st), "rd_dwconv_fwd_stats")
     else:
         _chk(lib.rd_dwconv_fwd(_p(x), _p(weight.detach()), _p(y), N, H, W, C, OH, OW, k, stride, pad, dt, st), "rd_dwconv_fwd")
+    bn_train = bn is not None and (training or not bn.track_running_stats)
     if bn is not None:
-        z, coef, bn_train = _bn_forward(y, bn, act, slope, None, training, stats=stats)
+        if bn_train and stats is None:      # (a shape whose convolution kernel has no statistics epilogue, or dw_fused_stats off)
+            stats = torch.empty((lib.rd_dw_rows(N * OH * OW, C), C, 2), dtype=torch.float32, device=x.device)
+            _chk(lib.rd_bn_stats(_p(y), _p(stats), N * OH * OW, C, dt, st), "rd_bn_stats")
+        z, coef = _bn_forward(y, bn, act, slope, None, stats, bn_train, _bn_slab(lib, y, stats, None), timed=False)
     else:
-        z, coef, bn_train = y, None, False
+        z, coef = y, None
         assert act == ACT_NONE
     if t is None or not (t.requires(x) or weight.requires_grad):
         return z
@@ -2344,7 +2374,7 @@ def dwconv_block(x, weight, *, stride=1, pad=0, out_hw=None, bn=None, act=ACT_NO
         if bn is not None:
             if not bn_train:
                 raise NotImplementedError("backward through eval-mode BatchNorm is not supported")
-            dy, _ = _bn_backward(t, dz, z, y, coef, bn, act, slope, False)
+            dy, _ = _bn_backward(t, dz, z, y, coef, bn, act, slope, False, False, timed=False)
         else:
             dy = dz
         if weight.requires_grad:

@@ -2360,3 +2360,275 @@ def point_mlp_case(dev, R=240, tol=TOL):
     (out * w.to(dev)).sum().backward()
     close(xd.grad, xr.grad, tol, "point MLP d points")
     assert compare_param_grads(m, sd, tol) == 12
+
+
+# ------------------------------------------------------------------------------------- conv_block's routes, pinned
+_ROUTE_QUERIES = ("_ok", "_rows", "_bytes", "_streams", "_kernel_name")
+_ROUTE_HOST = ("rd_last_error_string", "rd_set_option", "rd_clear_option", "rd_clear_options", "rd_conv_packed_elems")
+_ROUTE_ACTS = {None: 0, "relu": 1, "lrelu": 2, "relu6": 3}
+
+
+def _route_flags(args):
+    """which of a ConvDesc's gather / store forms and of a fusion struct's halves a call carries: "[d2s]", "[in]", "[reduce2,bn]" ..."""
+    from riders_amd import _lib as rlib
+    d = getattr(args[0], "_obj", None) if args else None
+    if not isinstance(d, rlib.ConvDesc):
+        return ""
+    flags = [n for n, f in (("up", "upsample"), ("d2s", "out_d2s"), ("s2d", "in_s2d"), ("reduce2", "out_reduce2")) if getattr(d, f)]
+    f = getattr(args[1], "_obj", None) if len(args) > 1 else None
+    if isinstance(f, rlib.ConvFusion):
+        flags += (["in"] if f.in_scale else []) + (["bn"] if f.bn_y else [])
+    return "[%s]" % ",".join(flags) if flags else ""
+
+
+class _RouteRecorder(object):
+    """Stands in for the bound library: every entry point that enqueues work is appended to `calls` by name (+ _route_flags) and passed on;
+    queries and host-side bookkeeping pass through unrecorded."""
+    def __init__(self, lib, calls):
+        self._lib, self._calls = lib, calls
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name.endswith(_ROUTE_QUERIES) or name in _ROUTE_HOST:
+            return fn
+
+        def call(*args):
+            self._calls.append(name + _route_flags(args))
+            return fn(*args)
+        return call
+
+
+def _route_ref_layer(l, val, par):
+    """one layer of a route case on the oracle's side: NCHW fp32 with the 16-bit mode's rounding points (oracle/precision.py), as
+    oracle.rcnet.conv_bn_act states them"""
+    from oracle.precision import Precision as PR
+    x = val[l["x"]]
+    if l["op"] == "linear":
+        y = F.linear(x, PR.w(par["w"]), par.get("b"))
+    elif l["op"] == "dw":
+        y = F.conv2d(x, par["w"], None, stride=l.get("s", 1), padding=l["k"] // 2, groups=x.shape[1])
+    else:
+        if l.get("x2"):
+            x = torch.cat([x, val[l["x2"]]], 1)
+        if l.get("up"):
+            x = PR.g(F.interpolate(x, size=l["up"]))
+        y = F.conv2d(x, PR.w(par["w"]), par.get("b"), stride=l.get("s", 1), padding=l["k"] // 2)
+    if l.get("bn"):
+        y = F.batch_norm(PR.r(y), par["rm"], par["rv"], par["g"], par["beta"], l["bn"] == "train", 0.1, 1e-5)
+    if l.get("res"):
+        y = y + val[l["res"]]
+    a = l.get("act")
+    y = F.leaky_relu(y, 0.2) if a == "lrelu" else (F.relu6(y) if a == "relu6" else (F.relu(y) if a == "relu" else y))
+    return PR.r(y)
+
+
+def _route_engine_layer(l, val, par, bn):
+    from riders_amd import engine
+    act = _ROUTE_ACTS[l.get("act")]
+    if l["op"] == "linear":
+        return engine.linear(val[l["x"]], par["w"], bias=par.get("b"), act=act)
+    if l["op"] == "dw":
+        return engine.dwconv_block(val[l["x"]], par["w"], stride=l.get("s", 1), pad=l["k"] // 2, bn=bn, act=act, slope=0.2, training=l.get("bn") != "eval")
+    lazy = l.get("lazy_out", 0)
+    if lazy == "head":
+        lazy = 1 if engine.head_route(l["cout"]) else 0
+    return engine.conv_block(val[l["x"]], par["w"], x2=val.get(l.get("x2")), bias=par.get("b"), stride=l.get("s", 1), pad=l["k"] // 2, up=l.get("up"), bn=bn,
+                             act=act, slope=0.2, residual=val.get(l.get("res")), training=l.get("bn") != "eval", lazy_out=lazy)
+
+
+def _route_params(tag, i, l, dev):
+    """-> (engine-side parameters, their BatchNorm2d container or None, oracle-side leaves) with identical values"""
+    cin, cout, k = l["cin"], l["cout"], l.get("k", 1)
+    shape = (cout, cin) if l["op"] == "linear" else ((cout, 1, k, k) if l["op"] == "dw" else (cout, cin, k, k))
+    fan = k * k * (1 if l["op"] == "dw" else cin)
+    vals = {"w": rand_array("%s.%d.w" % (tag, i), shape, (3.0 / fan) ** 0.5)}
+    if l.get("bias"):
+        vals["b"] = rand_array("%s.%d.b" % (tag, i), (cout,), 0.5)
+    bn = None
+    if l.get("bn"):
+        vals.update(g=rand_array("%s.%d.g" % (tag, i), (cout,), 0.5) + np.float32(1.0), beta=rand_array("%s.%d.beta" % (tag, i), (cout,), 0.5),
+                    rm=rand_array("%s.%d.rm" % (tag, i), (cout,), 0.1), rv=rand_array("%s.%d.rv" % (tag, i), (cout,), 0.5) + np.float32(1.0))
+        bn = torch.nn.BatchNorm2d(cout).to(dev)
+        with torch.no_grad():
+            bn.weight.copy_(t(vals["g"])); bn.bias.copy_(t(vals["beta"])); bn.running_mean.copy_(t(vals["rm"])); bn.running_var.copy_(t(vals["rv"]))
+    par = {n: torch.nn.Parameter(t(v, dev)) for n, v in vals.items() if n in ("w", "b")}
+    if bn is not None:
+        par.update(g=bn.weight, beta=bn.bias, rm=bn.running_mean, rv=bn.running_var)
+    ref = {n: t(v).clone().requires_grad_(n not in ("rm", "rv")) for n, v in vals.items()}
+    return par, bn, ref
+
+
+def _route_to_ref(a):
+    return a.float().permute(0, 3, 1, 2).cpu() if a.dim() == 4 else a.float().cpu()
+
+
+def route_case(dev, c):
+    """One entry of ROUTE_CASES: a few layers driven through engine.conv_block / dwconv_block / linear on a tape of their own, forward through
+    tape.backward() and the deferred flushes.  Asserts (1) the ordered entry points that enqueued work (_RouteRecorder) against the literal
+    c["calls"] -- the route, pinned -- (2) engine.lazy_counts where the case names them, and (3) outputs, input gradients, parameter gradients
+    and BatchNorm running statistics against the oracle's arithmetic: 1e-3 of max in fp32 (as conv_case), 2e-2 in the 16-bit mode (the
+    2.5 bf16 ulp of the one-layer oracle comparisons, stem_kernel_cases, for two chained layers)."""
+    import contextlib
+    from riders_amd import engine, _lib as rlib
+    tag, half = "route." + c["name"], c.get("mode", "fp32") != "fp32"
+    tol = 2e-2 if half else TOL
+    old = {k: engine.switch(k) for k in list(c.get("switches", {})) + list(c.get("bwd_switches", {}))}
+    calls = []
+    with contextlib.ExitStack() as stack:
+        if half:
+            m = bf16_mode(c["mode"]); m.__enter__(); stack.push(m.__exit__)
+        if c.get("force"):
+            f = c["force"](); f.__enter__(); stack.push(f.__exit__)
+        orig = rlib._lib
+        try:
+            for k, v in c.get("switches", {}).items():
+                engine.set_switch(k, v)
+            for k in engine.lazy_counts:
+                engine.lazy_counts[k] = 0
+            ref, val, tape = {}, {}, engine.Tape()
+            for name, (shape, req) in c["inputs"].items():
+                x = q(t(rand_array("%s.%s" % (tag, name), shape, 1.0)))
+                ref[name] = x.clone().requires_grad_(req)
+                a = x.to(dev)
+                val[name] = (a.permute(0, 2, 3, 1).contiguous() if a.dim() == 4 else a).to(engine.act_dtype())
+                if req:
+                    tape.mark(val[name])
+            pars = [_route_params(tag, i, l, dev) for i, l in enumerate(c["layers"])]
+            rlib._lib = _RouteRecorder(orig, calls)
+            with engine._active(tape):
+                for l, (par, bn, _) in zip(c["layers"], pars):
+                    val[l["out"]] = _route_engine_layer(l, val, par, bn)
+                seeds = {}
+                for o in c["outs"]:
+                    seeds[o] = q(t(rand_array("%s.%s.g" % (tag, o), tuple(_route_to_ref(val[o]).shape), 1.0)))
+                    g = seeds[o].to(dev)
+                    tape.grads[id(val[o])] = (g.permute(0, 2, 3, 1).contiguous() if g.dim() == 4 else g).to(engine.act_dtype())
+                for k, v in c.get("bwd_switches", {}).items():      # (flipped between the forward and the backward)
+                    engine.set_switch(k, v)
+                if c.get("raises"):
+                    try:
+                        tape.backward()
+                    except c["raises"][0] as e:
+                        assert str(e) == c["raises"][1], e
+                    else:
+                        raise AssertionError("%s: backward did not raise" % tag)
+                else:
+                    tape.backward()
+        finally:
+            rlib._lib = orig
+            for k, v in old.items():
+                engine.set_switch(k, v)
+        counts = dict(engine.lazy_counts)
+        for l, (_, _, rp) in zip(c["layers"], pars):
+            ref[l["out"]] = _route_ref_layer(l, ref, rp)
+        if not c.get("raises"):
+            sum((ref[o] * seeds[o]).sum() for o in c["outs"]).backward()
+    print("%s: %r %r" % (tag, calls, {k: v for k, v in counts.items() if v}))
+    for o in c["outs"]:
+        close(_route_to_ref(val[o]), ref[o], tol, tag + " output " + o)
+    for l, (par, bn, rp) in zip(c["layers"], pars):
+        if bn is not None and l["bn"] == "train":
+            close(bn.running_mean, rp["rm"], tol, tag + " running_mean"); close(bn.running_var, rp["rv"], tol, tag + " running_var")
+        for n in ("w", "b", "g", "beta"):
+            if n in par and not c.get("raises"):
+                close(tape.pgrads[id(par[n])], rp[n].grad, tol, "%s grad of %s.%s" % (tag, l["out"], n))
+    for name, (_, req) in c["inputs"].items():
+        if req and not c.get("raises"):
+            close(_route_to_ref(tape.grads[id(val[name])]), ref[name].grad, tol, tag + " gradient of " + name)
+    assert calls == c["calls"], "%s: launches\n  %r\nexpected\n  %r" % (tag, calls, c["calls"])
+    for k, v in c.get("counts", {}).items():
+        assert counts[k] == v, (tag, k, counts)
+
+
+def _rl(op, x, out, cin, cout, **kw):
+    return dict(op=op, x=x, out=out, cin=cin, cout=cout, **kw)
+
+
+def _route_opts(**opts):
+    f = _force_options()
+    f.opts = opts
+    return f
+
+
+_X16 = {"x": ((2, 16, 9, 7), True)}
+_BN16 = dict(k=3, bn="train", act="lrelu")
+_UP = {"x": ((2, 32, 5, 4), True)}
+_FRAG = {"x": ((2, 32, 15, 16), True)}
+
+# name, inputs {name: (NCHW or (rows, C) shape, needs a gradient)}, layers, outs (seeded with a gradient), switches / force / mode, and the pinned
+# launch sequence `calls` (recorded at the commit before conv_block was split into stages; written out by hand)
+ROUTE_CASES = [
+    dict(name="plain", inputs=_X16, layers=[_rl("conv", "x", "y", 16, 16, k=3, act="lrelu")], outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_act_bwd", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="linear_deferred", inputs={"x": ((35, 32), True)}, layers=[_rl("linear", "x", "y", 32, 48, bias=True)], outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_colsum_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_colsum_finalize_batch", "rd_linear_wgrad_batch"]),
+    dict(name="linear_direct", inputs={"x": ((35, 32), True)}, layers=[_rl("linear", "x", "y", 32, 48, bias=True)], outs=["y"], switches={"defer_wgrad": False},
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_colsum", "rd_conv_wgrad", "rd_conv_pack_weights", "rd_conv_fwd"]),
+    dict(name="bn_act", inputs=_X16, layers=[_rl("conv", "x", "y", 16, 16, **_BN16)], outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="bn_act_residual", inputs=dict(_X16, r=((2, 16, 9, 7), True)), layers=[_rl("conv", "x", "y", 16, 16, res="r", **_BN16)], outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="bn_slab", inputs={"x": ((2, 8, 5, 4), True)}, layers=[_rl("conv", "x", "y", 8, 256, k=1, bn="train", act="relu6")], outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize_apply", "rd_bn_act_bwd_slab", "rd_conv_pack_weights", "rd_conv_fwd", "rd_linear_wgrad_batch"]),
+    dict(name="bn_slab_lazy_out", inputs={"x": ((2, 8, 5, 4), True)},
+         layers=[_rl("conv", "x", "h", 8, 256, k=1, bn="train", act="relu6", lazy_out=2), _rl("conv", "h", "y", 256, 8, k=1)], outs=["y"], switches={"lazy_bn": 2},
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_act_bwd_slab", "rd_conv_pack_weights", "rd_conv_fwd", "rd_linear_wgrad_batch"]),
+    dict(name="bn_eval", inputs=_X16, layers=[_rl("conv", "x", "y", 16, 16, k=3, bn="eval", act="lrelu")], outs=["y"],
+         raises=(NotImplementedError, "backward through eval-mode BatchNorm is not supported"),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act"]),
+    dict(name="lazy_in_fused", mode="bf16", force=lambda: force_frag_conv(lin=0), inputs={"x": ((2, 64, 15, 16), True)},
+         layers=[_rl("conv", "x", "h", 64, 64, lazy_out=1, **_BN16), _rl("conv", "h", "y", 64, 64, **_BN16)], outs=["y"],
+         counts=dict(fwd_fused=1, wgrad_fused=1, materialized=0),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_conv_pack_weights", "rd_conv_fwd_fused[in]", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_conv_wgrad_partial_fused[in]", "rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_act_bwd_recompute", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="lazy_in_refused", inputs=_X16, layers=[_rl("conv", "x", "h", 16, 16, lazy_out=1, **_BN16), _rl("conv", "h", "y", 16, 16, k=1)], outs=["y"],
+         counts=dict(fwd_fused=0, materialized=1),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_act_bwd_recompute", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch", "rd_linear_wgrad_batch"]),
+    dict(name="head", inputs={"x": ((2, 16, 12, 9), True)}, layers=[_rl("conv", "x", "h", 16, 16, lazy_out="head", **_BN16), _rl("conv", "h", "y", 16, 1, k=3)],
+         outs=["y"], counts=dict(head_fused=1, head_unfused_bwd=0),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_bn_head_fwd", "rd_bn_head_bwd_reduce", "rd_bn_head_bwd_apply", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="head_no_recompute", inputs={"x": ((2, 16, 12, 9), True)}, switches={"bn_recompute": False},
+         layers=[_rl("conv", "x", "h", 16, 16, lazy_out="head", **_BN16), _rl("conv", "h", "y", 16, 1, k=3)], outs=["y"],
+         counts=dict(head_fused=0, head_unfused_bwd=0),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_act_bwd", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="head_second_consumer", inputs={"x": ((2, 16, 12, 9), True)},
+         layers=[_rl("conv", "x", "h", 16, 16, lazy_out="head", **_BN16), _rl("conv", "h", "y", 16, 1, k=3), _rl("conv", "h", "y2", 16, 8, k=3)], outs=["y", "y2"],
+         counts=dict(head_fused=1, head_unfused_bwd=1),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_bn_head_fwd", "rd_affine_act", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_wgrad", "rd_conv_pack_weights", "rd_conv_fwd", "rd_add", "rd_bn_act_bwd_recompute", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="up2_on_source", mode="bf16", force=force_patch_conv, inputs=_UP, layers=[_rl("conv", "x", "y", 32, 16, k=3, up=(10, 8))], outs=["y"],
+         counts=dict(up2_fwd=1, up2_dgrad=1),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd[d2s]", "rd_conv_wgrad_partial[up]", "rd_conv_pack_weights", "rd_conv_pack_weights", "rd_conv_fwd[s2d]", "rd_wgrad_reduce_batch"]),
+    dict(name="up2_reduce2", mode="bf16", force=force_patch_conv, inputs=_UP, layers=[_rl("conv", "x", "y", 32, 16, k=3, up=(10, 8))], outs=["y"], switches={"up2_dgrad": False},
+         counts=dict(up2_fwd=1, up2_dgrad=0),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd[d2s]", "rd_conv_wgrad_partial[up]", "rd_conv_pack_weights", "rd_conv_fwd[reduce2]", "rd_wgrad_reduce_batch"]),
+    dict(name="up2_plain_dgrad", mode="bf16", force=force_patch_conv, inputs=_UP, layers=[_rl("conv", "x", "y", 32, 16, k=3, up=(10, 8))], outs=["y"],
+         switches={"up2_dgrad": False, "fuse_upsample_bwd": False},
+         calls=["rd_conv_pack_weights", "rd_conv_fwd[d2s]", "rd_conv_wgrad_partial[up]", "rd_conv_pack_weights", "rd_conv_fwd", "rd_upsample_nearest_bwd", "rd_wgrad_reduce_batch"]),
+    dict(name="up_concat", force=force_patch_conv, inputs=dict(_UP, s=((2, 16, 5, 4), True)), layers=[_rl("conv", "x", "y", 48, 16, x2="s", k=3, up=(10, 8))],
+         outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd[up]", "rd_conv_wgrad_partial[up]", "rd_conv_pack_weights", "rd_conv_fwd", "rd_upsample_nearest_bwd", "rd_upsample_nearest_bwd", "rd_wgrad_reduce_batch"]),
+    dict(name="stem_padded", inputs={"x": ((2, 3, 20, 18), False)}, layers=[_rl("conv", "x", "y", 3, 32, k=7, s=2, bn="train", act="lrelu")], outs=["y"],
+         calls=["rd_pad_channels", "rd_conv_pack_weights_padded", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_conv_wgrad", "rd_unpad_weight_grad"]),
+    dict(name="stem_padded_streaming_wgrad", force=lambda: _route_opts(wgrad_tiny_min_m=0), inputs={"x": ((2, 3, 19, 12), False)},
+         layers=[_rl("conv", "x", "y", 3, 3, k=3, bn="train", act="lrelu")], outs=["y"],
+         calls=["rd_pad_channels", "rd_conv_pack_weights_padded", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_conv_wgrad"]),
+    dict(name="stem_streaming", force=lambda: force_tiny_wgrad(), inputs={"x": ((2, 3, 19, 12), False)},
+         layers=[_rl("conv", "x", "y", 3, 3, k=3, bn="train", act="lrelu")], outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_conv_wgrad_partial", "rd_wgrad_reduce_batch"]),
+    dict(name="residual_in_epilogue", force=lambda: force_frag_conv(), inputs=dict(_FRAG, r=((2, 32, 15, 16), True)),
+         layers=[_rl("conv", "x", "y", 32, 32, k=3, bias=True, res="r")], outs=["y"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd_add", "rd_colsum_partial", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_colsum_finalize_batch", "rd_wgrad_reduce_batch"]),
+    dict(name="two_consumers", force=lambda: force_frag_conv(), inputs=_FRAG,
+         layers=[_rl("conv", "x", "a", 32, 32, k=3), _rl("conv", "x", "b", 32, 32, k=3)], outs=["a", "b"],
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd_add", "rd_wgrad_reduce_batch"]),
+    dict(name="bn_bwd_fused", force=lambda: force_frag_conv(lin=0), inputs=_FRAG, switches={"bn_bwd_fused": True},
+         layers=[_rl("conv", "x", "h", 32, 32, lazy_out=1, **_BN16), _rl("conv", "h", "y", 32, 32, **_BN16)], outs=["y"], counts=dict(bn_bwd_fused=1),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_conv_pack_weights", "rd_conv_fwd_fused[in]", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_affine_act", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd_fused[bn]", "rd_bn_act_bwd_from_partial", "rd_conv_wgrad_partial", "rd_conv_pack_weights", "rd_conv_fwd", "rd_wgrad_reduce_batch"]),
+    dict(name="dw_fused_stats", inputs=_X16, layers=[_rl("dw", "x", "y", 16, 16, k=3, bn="train", act="relu6")], outs=["y"],
+         calls=["rd_dwconv_fwd_stats", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_dwconv_wgrad_partial", "rd_dwconv_dgrad", "rd_dw_wgrad_finalize_batch"]),
+    dict(name="dw_separate_stats", inputs=_X16, layers=[_rl("dw", "x", "y", 16, 16, k=3, bn="train", act="relu6")], outs=["y"], switches={"dw_fused_stats": False},
+         calls=["rd_dwconv_fwd", "rd_bn_stats", "rd_bn_finalize", "rd_affine_act", "rd_bn_act_bwd_recompute", "rd_dwconv_wgrad_partial", "rd_dwconv_dgrad", "rd_dw_wgrad_finalize_batch"]),
+    dict(name="dw_slab", inputs={"x": ((2, 256, 5, 4), True)}, layers=[_rl("dw", "x", "y", 256, 256, k=3, bn="train", act="relu6")], outs=["y"],
+         calls=["rd_dwconv_fwd_stats", "rd_bn_finalize_apply", "rd_bn_act_bwd_slab", "rd_dwconv_wgrad_partial", "rd_dwconv_dgrad", "rd_dw_wgrad_finalize_batch"]),
+    dict(name="dw_no_bn", inputs=_X16, layers=[_rl("dw", "x", "y", 16, 16, k=3, s=2)], outs=["y"],
+         calls=["rd_dwconv_fwd", "rd_dwconv_wgrad_partial", "rd_dwconv_dgrad", "rd_dw_wgrad_finalize_batch"]),
+]

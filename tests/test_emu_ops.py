@@ -292,3 +292,10 @@ def test_pointwise_gemm_kernel(emu):
 
 def test_bn_one_launch_wide_layers(emu):
     P.bn_slab_cases(emu)
+
+
+@pytest.mark.parametrize("case", [c["name"] for c in P.ROUTE_CASES])
+def test_conv_block_routes(emu, case):
+    """Which launches each route of conv_block / dwconv_block / linear enqueues, forward through backward and the deferred flushes, against literal
+    sequences (parity_cases.ROUTE_CASES), and the results against the oracle."""
+    P.route_case(emu, next(c for c in P.ROUTE_CASES if c["name"] == case))

@@ -764,3 +764,9 @@ def test_pointwise_gemm_kernel(gpu):
 
 def test_bn_one_launch_wide_layers(gpu):
     P.bn_slab_cases(gpu)
+
+
+@pytest.mark.parametrize("case", [c["name"] for c in P.ROUTE_CASES])
+def test_conv_block_routes(gpu, case):
+    """The emulator's route table (tests/test_emu_ops.py) against the real library: the same launch sequences, the same oracle comparison."""
+    P.route_case(gpu, next(c for c in P.ROUTE_CASES if c["name"] == case))
