@@ -647,6 +647,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict_
     float s = 0.f;
     for (int e = 0; e < epl; e++) { v[e] = Elem<T>::ld(x + r * C + e * 64 + lane); s += v[e]; }
     float mu = wave_sum(s) / (float)C;
+    // the sum is C times the size of its terms and carries that rounding into the mean: (x - mu) * rstd was 2e-4 off for rows of mean 100 and
+    // spread 0.1.  The first mean, cut to its top 8 significant bits so that x - mu stays exact, plus the mean of the residuals
+    mu = __uint_as_float(__float_as_uint(mu) & 0xffff0000u);
+    float dm = 0.f;
+    for (int e = 0; e < epl; e++) dm += v[e] - mu;
+    mu += wave_sum(dm) / (float)C;
     float q = 0.f;
     for (int e = 0; e < epl; e++) { float d = v[e] - mu; q += d * d; }
     float var = wave_sum(q) / (float)C;
