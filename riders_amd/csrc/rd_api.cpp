@@ -326,7 +326,15 @@ const char* rd_conv_fused_kernel_name(const rd_conv_desc* d, const rd_conv_fusio
   if (!apply_fusion(d, f, a)) return "";
   return RD_NS(d->dtype, conv_kernel_name)(a, RD_DT(d->dtype));
 }
-static void fill_wgrad_args(const rd_conv_desc* d, rd::WgradArgs& a);
+static void fill_wgrad_args(const rd_conv_desc* d, rd::WgradArgs& a) {
+  memset(&a, 0, sizeof(a));
+  a.N = d->N; a.Hin = d->Hin; a.Win = d->Win; a.C1 = d->C1; a.C2 = d->C2;
+  a.ups = d->upsample ? 1 : 0; a.H1 = a.ups ? d->H1 : d->Hin; a.W1 = a.ups ? d->W1 : d->Win;
+  a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.OH = d->OH; a.OW = d->OW;
+  a.scale_h = (float)a.H1 / (float)d->Hin; a.scale_w = (float)a.W1 / (float)d->Win;
+  a.M = d->N * d->OH * d->OW;
+  a.K = d->KH * d->KW * (d->C1 + d->C2);
+}
 const char* rd_conv_wgrad_kernel_name(const rd_conv_desc* d) {
   if (!d || check_desc(d) || d->in_dilate != 1) return "";
   rd::WgradArgs a; fill_wgrad_args(d, a);
@@ -338,24 +346,9 @@ const char* rd_conv_wgrad_fused_kernel_name(const rd_conv_desc* d, const rd_conv
   if (f && f->in_scale) { a.in_scale = f->in_scale; a.in_shift = f->in_shift; }
   return RD_NS(d->dtype, wgrad_kernel_name)(a, RD_DT(d->dtype));
 }
-static void fill_wgrad_args(const rd_conv_desc* d, rd::WgradArgs& a) {
-  memset(&a, 0, sizeof(a));
-  a.N = d->N; a.Hin = d->Hin; a.Win = d->Win; a.C1 = d->C1; a.C2 = d->C2;
-  a.ups = d->upsample ? 1 : 0; a.H1 = a.ups ? d->H1 : d->Hin; a.W1 = a.ups ? d->W1 : d->Win;
-  a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.OH = d->OH; a.OW = d->OW;
-  a.scale_h = (float)a.H1 / (float)d->Hin; a.scale_w = (float)a.W1 / (float)d->Win;
-  a.M = d->N * d->OH * d->OW;
-  a.K = d->KH * d->KW * (d->C1 + d->C2);
-}
 int64_t rd_conv_wgrad_workspace_bytes(const rd_conv_desc* d) {
   rd::WgradArgs a; fill_wgrad_args(d, a);
-  int ns = rd::wgrad_slabs(a.M, a.K, d->Cout);
-  if (RD_NS(d->dtype, wgrad3x3_tr_ok)(a, RD_DT(d->dtype))) ns = std::max(ns, rd::wgrad3x3_tr_blocks(a));
-  // the same shape with a consumer-side BatchNorm apply runs on the 8 x TW kernel even where the map-fitted one takes the plain launch
-  static const float kDummy = 0.f;
-  a.in_scale = &kDummy;
-  if (RD_NS(d->dtype, wgrad3x3_tr_ok)(a, RD_DT(d->dtype))) ns = std::max(ns, rd::wgrad3x3_tr_blocks(a));
-  a.in_scale = nullptr;
+  const int ns = RD_NS(d->dtype, wgrad_workspace_slabs)(a, RD_DT(d->dtype));
   return (int64_t)(ns + 1) * d->Cout * a.K * (int64_t)sizeof(float);
 }
 int64_t rd_workspace_bytes(int32_t op, const rd_conv_desc* d) {
@@ -375,21 +368,15 @@ int rd_conv_wgrad(const rd_conv_desc* d, const void* src1, const void* src2, con
   if (int e = check_desc(d)) return e;
   if (!src1 || !dy || !workspace || !dw) return fail("conv_wgrad: null pointer");
   if (d->in_dilate != 1) return fail("conv_wgrad: in_dilate must be 1");
-  rd::WgradArgs a; memset(&a, 0, sizeof(a));
+  rd::WgradArgs a; fill_wgrad_args(d, a);
   a.src1 = src1; a.src2 = src2; a.dy = dy; a.slab = workspace;
-  a.N = d->N; a.Hin = d->Hin; a.Win = d->Win; a.C1 = d->C1; a.C2 = d->C2;
-  a.ups = d->upsample ? 1 : 0; a.H1 = a.ups ? d->H1 : d->Hin; a.W1 = a.ups ? d->W1 : d->Win;
-  a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.OH = d->OH; a.OW = d->OW;
-  a.scale_h = (float)a.H1 / (float)d->Hin; a.scale_w = (float)a.W1 / (float)d->Win;
-  a.M = d->N * d->OH * d->OW; a.K = d->KH * d->KW * (d->C1 + d->C2);
   RD_NS(d->dtype, launch_wgrad)(a, RD_DT(d->dtype), dw, accumulate, S(stream), nullptr);
   return done("rd_conv_wgrad");
 }
 int32_t rd_conv_wgrad_streams(const rd_conv_desc* d) {
   if (!d || check_desc(d) || d->in_dilate != 1) return 0;
   rd::WgradArgs a; fill_wgrad_args(d, a);
-  a.C1 = d->C1; a.C2 = d->C2; a.ups = d->upsample ? 1 : 0; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.Cout = d->Cout;
-  return RD_NS(d->dtype, wgrad_streams)(a) ? 1 : 0;
+  return RD_NS(d->dtype, wgrad_streams)(a, RD_DT(d->dtype)) ? 1 : 0;
 }
 static_assert(sizeof(rd_wgrad_reduce_item) == sizeof(rdt::WgradReduceItem), "rd_wgrad_reduce_item layout");
 int rd_conv_wgrad_partial(const rd_conv_desc* d, const void* src1, const void* src2, const void* dy, float* workspace, float* dw,
@@ -397,13 +384,8 @@ int rd_conv_wgrad_partial(const rd_conv_desc* d, const void* src1, const void* s
   if (int e = check_desc(d)) return e;
   if (!src1 || !dy || !workspace || !dw || !item) return fail("conv_wgrad_partial: null pointer");
   if (d->in_dilate != 1) return fail("conv_wgrad_partial: in_dilate must be 1");
-  rd::WgradArgs a; memset(&a, 0, sizeof(a));
+  rd::WgradArgs a; fill_wgrad_args(d, a);
   a.src1 = src1; a.src2 = src2; a.dy = dy; a.slab = workspace;
-  a.N = d->N; a.Hin = d->Hin; a.Win = d->Win; a.C1 = d->C1; a.C2 = d->C2;
-  a.ups = d->upsample ? 1 : 0; a.H1 = a.ups ? d->H1 : d->Hin; a.W1 = a.ups ? d->W1 : d->Win;
-  a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.OH = d->OH; a.OW = d->OW;
-  a.scale_h = (float)a.H1 / (float)d->Hin; a.scale_w = (float)a.W1 / (float)d->Win;
-  a.M = d->N * d->OH * d->OW; a.K = d->KH * d->KW * (d->C1 + d->C2);
   RD_NS(d->dtype, launch_wgrad)(a, RD_DT(d->dtype), dw, accumulate, S(stream), reinterpret_cast<rdt::WgradReduceItem*>(item));
   return done("rd_conv_wgrad_partial");
 }

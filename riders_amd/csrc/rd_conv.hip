@@ -1162,49 +1162,44 @@ static void conv_tiles(int M, int Cout, int& bn, int& wm) {
     if (bn == 64 && cdiv(M, 64) * cdiv(Cout, bn) < 128) bn = 32;
   }
 }
-int conv_block_pixels(int M, int Cout) { int bn, wm; conv_tiles(M, Cout, bn, wm); return 32 * wm; }
 
 // parity-class walk of a stride-2 layer's data gradient (conv_gemm_kernel PAR): whole 128-byte channel stages, one source, no statistics
 static bool conv_gemm_par(const ConvArgs& a, int dtype) {
   const int bke = STAGE_BYTES / (dtype == 0 ? 4 : 2), Cin = a.C1 + a.C2;
-  const bool off = rd_opt(OPT_CONV_PAR, 1) == 0;      // A/B switch (rd_set_option)
-  return !off && a.dil == 2 && a.stride == 1 && !a.ups && a.C2 == 0 && Cin % bke == 0 && !a.stats && !a.pool2 && a.K == a.KH * a.KW * Cin &&
+  return rd_opt(OPT_CONV_PAR, 1) != 0 /* A/B switch (rd_set_option) */ && a.dil == 2 && a.stride == 1 && !a.ups && a.C2 == 0 && Cin % bke == 0 && !a.stats && !a.pool2 && a.K == a.KH * a.KW * Cin &&
          a.Kpad == a.K;
 }
-static bool conv_gemm_deep(const ConvArgs& a, int dtype) {
-  const int ve = dtype == 0 ? 4 : 8, Cin = a.C1 + a.C2, es = dtype == 0 ? 4 : 2;
-  const bool vec = (Cin % ve == 0) && (a.C1 % ve == 0);
-  int bn, wm;
-  conv_tiles(a.M, a.Cout, bn, wm);
-  int nk = a.Kpad / (STAGE_BYTES / es);
-  if (conv_gemm_par(a, dtype)) nk = ((a.KH + 1) / 2) * ((a.KW + 1) / 2) * (Cin / (STAGE_BYTES / es));      // the longest class
-  return vec && wm == 2 && cdiv(a.M, 32 * wm) * cdiv(a.Cout, bn) <= 512 && nk >= 6;
+// the implicit-GEMM kernel's instantiation and grid for a descriptor: read by the launcher and by the name query
+struct GemmPlan { int bn, wm; bool vec, deep, par; dim3 grid; };
+static GemmPlan conv_gemm_plan(const ConvArgs& a, int dtype) {
+  const int es = dtype == 0 ? 4 : 2, ve = 16 / es, bke = STAGE_BYTES / es, Cin = a.C1 + a.C2;
+  GemmPlan p;
+  conv_tiles(a.M, a.Cout, p.bn, p.wm);
+  p.vec = (Cin % ve == 0) && (a.C1 % ve == 0);
+  p.par = conv_gemm_par(a, dtype);
+  p.grid = dim3((unsigned)cdiv(a.M, 32 * p.wm), (unsigned)cdiv(a.Cout, p.bn));
+  int nk = a.Kpad / bke;
+  if (p.par) {      // the tiles of the four parity classes, one after the other; the K walk of the longest class
+    p.grid.x = 0;
+    for (int c = 0; c < 4; c++) { int ph, pw, oh2, ow2, mc; par_class(c, a.OH, a.OW, a.N, ph, pw, oh2, ow2, mc); p.grid.x += (unsigned)cdiv(mc, 32 * p.wm); }
+    nk = ((a.KH + 1) / 2) * ((a.KW + 1) / 2) * (Cin / bke);
+  }
+  // few blocks and a long K axis: latency-bound stage chain -> two-stage-ahead loads
+  p.deep = p.vec && p.wm == 2 && cdiv(a.M, 32 * p.wm) * cdiv(a.Cout, p.bn) <= 512 && nk >= 6;
+  return p;
 }
 template <typename T>
 static void launch_conv_t(const ConvArgs& a, hipStream_t st) {
-  constexpr int VE = Elem<T>::VE;
-  const int Cin = a.C1 + a.C2;
-  const bool vec = (Cin % VE == 0) && (a.C1 % VE == 0);
-  int bn, wm;
-  conv_tiles(a.M, a.Cout, bn, wm);
-  dim3 grid((unsigned)cdiv(a.M, 32 * wm), (unsigned)cdiv(a.Cout, bn));
-  const bool par = conv_gemm_par(a, sizeof(T) == 4 ? 0 : 1);
-  if (par) {      // the tiles of the four parity classes, one after the other
-    unsigned gx = 0;
-    for (int c = 0; c < 4; c++) { int ph, pw, oh2, ow2, mc; par_class(c, a.OH, a.OW, a.N, ph, pw, oh2, ow2, mc); gx += (unsigned)cdiv(mc, 32 * wm); }
-    grid.x = gx;
+  const GemmPlan p = conv_gemm_plan(a, sizeof(T) == 4 ? 0 : 1);
+#define RD_CONV_CASE(BNV, WMV)                                                                                      \
+  if (p.bn == BNV && p.wm == WMV) {                                                                                  \
+    if (p.par) hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, WMV, false, true>), p.grid, dim3(256), 0, st, a);  \
+    else if (p.vec) hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, WMV>), p.grid, dim3(256), 0, st, a);         \
+    else hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, false, WMV>), p.grid, dim3(256), 0, st, a);                   \
   }
-  // few blocks and a long K axis: latency-bound stage chain -> two-stage-ahead loads
-  const bool deep = conv_gemm_deep(a, sizeof(T) == 4 ? 0 : 1);
-#define RD_CONV_CASE(BNV, WMV)                                                                                  \
-  if (bn == BNV && wm == WMV) {                                                                                  \
-    if (par) hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, WMV, false, true>), grid, dim3(256), 0, st, a);  \
-    else if (vec) hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, WMV>), grid, dim3(256), 0, st, a);         \
-    else hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, false, WMV>), grid, dim3(256), 0, st, a);                 \
-  }
-#define RD_CONV_DEEP(BNV) if (bn == BNV) { if (par) hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, 2, true, true>), grid, dim3(256), 0, st, a); \
-                                            else hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, 2, true>), grid, dim3(256), 0, st, a); return; }
-  if (deep) { RD_CONV_DEEP(32) RD_CONV_DEEP(64) RD_CONV_DEEP(128) }
+#define RD_CONV_DEEP(BNV) if (p.bn == BNV) { if (p.par) hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, 2, true, true>), p.grid, dim3(256), 0, st, a); \
+                                              else hipLaunchKernelGGL((conv_gemm_kernel<T, BNV, true, 2, true>), p.grid, dim3(256), 0, st, a); return; }
+  if (p.deep) { RD_CONV_DEEP(32) RD_CONV_DEEP(64) RD_CONV_DEEP(128) }
 #undef RD_CONV_DEEP
   RD_CONV_CASE(16, 4) RD_CONV_CASE(32, 4) RD_CONV_CASE(64, 4) RD_CONV_CASE(128, 4)
   RD_CONV_CASE(32, 2) RD_CONV_CASE(64, 2) RD_CONV_CASE(128, 2)
@@ -1212,9 +1207,7 @@ static void launch_conv_t(const ConvArgs& a, hipStream_t st) {
 }
 
 // 3x3/stride-1 layers with enough tiles to fill the chip go to the patch-staged kernel (rd_conv3x3.hip)
-static int conv3x3_min_blocks() {
-  return rd_opt(OPT_CONV3X3_MIN_BLOCKS, 256);  // test hook (rd_set_option): 0 forces the patch kernel on small cases
-}
+static int conv3x3_min_blocks() { return rd_opt(OPT_CONV3X3_MIN_BLOCKS, 256); }      // test hook (rd_set_option): 0 forces the patch kernel on small cases
 static bool use_conv3x3(const ConvArgs& a, int dtype) {
   if (!conv3x3_ok(a, dtype)) return false;
   return (int64_t)conv3x3_tiles(a) * cdiv(a.Cout, pick_bn(a.Cout)) >= conv3x3_min_blocks();
@@ -1226,30 +1219,6 @@ static bool use_conv3x3_frag(const ConvArgs& a, int dtype) {   // wide layers: w
   // also far below one block per CU: a block's chain (patch load, 9 taps per chunk, store) is short next to the implicit-GEMM kernel's
   // stage chain on the same shape -- deep encoder stages, 9 672 / 2 560 pixels x 128 channels: 21 -> 13 us and 15 -> 12 us per launch
   return conv3x3_frag_ok(a, dtype) && conv3x3_frag_blocks(a, dtype) >= std::min(conv3x3_min_blocks(), 8);
-}
-static bool conv_stem_ok(const ConvArgs& a, int dtype);
-static int conv_stem_blocks(const ConvArgs& a);
-// rd_conv_pw.hip: pointwise layers on a few thousand pixels
-bool conv_pw_shape(const ConvArgs& a, int dtype);
-bool conv_pw_ok(const ConvArgs& a, int dtype);
-int conv_pw_rows(const ConvArgs& a);
-const char* conv_pw_name(const ConvArgs& a, int dtype);
-void launch_conv_pw(const ConvArgs& a, int dtype, hipStream_t st);
-static bool conv_skinny_ok(const ConvArgs& a, int dtype);
-static bool conv_pw_route(const ConvArgs& a, int dtype) {      // as launch_conv orders its routes
-  return !conv_skinny_ok(a, dtype) && !conv_stem_ok(a, dtype) && !conv_few_ok(a) && !conv1x1_direct_ok(a, dtype) && conv_pw_ok(a, dtype);
-}
-static bool conv_d2s_small(const ConvArgs& a, int dtype);
-int conv_stats_rows(const ConvArgs& a, int dtype) {
-  if (a.d2s) return conv_d2s_small(a, dtype) ? conv3x3_small_blocks(a, dtype) : conv3x3_frag_tiles(a, dtype);
-  if (conv_stem_ok(a, dtype)) return conv_stem_blocks(a);
-  if (conv_few_ok(a)) return conv_few_blocks(a);
-  if (conv1x1_direct_ok(a, dtype)) return conv1x1_direct_rows(a);
-  if (conv_pw_route(a, dtype)) return conv_pw_rows(a);
-  if (use_conv3x3_small(a, dtype)) return conv3x3_small_blocks(a, dtype);   // persistent blocks: one statistics row each
-  if (use_conv3x3_frag(a, dtype)) return conv3x3_frag_tiles(a, dtype);
-  if (use_conv3x3(a, dtype)) return conv3x3_tiles(a);
-  return (int)cdiv(a.M, conv_block_pixels(a.M, a.Cout));
 }
 
 // ---- skinny linear layers: few output tiles, long K axis ----------------------------------------------------------------------------
@@ -1409,33 +1378,69 @@ static void launch_conv_stem(const ConvArgs& a, int dtype, hipStream_t st) {
 #undef RD_STEM
 }
 
-void launch_conv(const ConvArgs& a, int dtype, hipStream_t st) {
-  if (a.s2d) { launch_conv3x3_frag(a, dtype, st); return; }      // (rd_api.cpp checked conv_s2d_ok)
-  if (a.d2s) { if (conv_d2s_small(a, dtype)) launch_conv3x3_small(a, dtype, st); else launch_conv3x3_frag(a, dtype, st); return; }      // (rd_api.cpp checked conv_d2s_ok)
-  if (conv_skinny_ok(a, dtype)) { launch_linear_skinny(a, dtype, st); return; }
-  if (conv_stem_ok(a, dtype)) { launch_conv_stem(a, dtype, st); return; }
-  if (conv_few_ok(a)) { launch_conv_few(a, dtype, st); return; }
-  if (conv1x1_direct_ok(a, dtype)) { launch_conv1x1_direct(a, dtype, st); return; }
-  if (conv_pw_ok(a, dtype)) { launch_conv_pw(a, dtype, st); return; }
-  if (conv3x3_c1_ok(a)) { launch_conv3x3_c1(a, dtype, st); return; }
-  if (use_conv3x3_small(a, dtype)) { launch_conv3x3_small(a, dtype, st); return; }
-  if (use_conv3x3_frag(a, dtype)) { launch_conv3x3_frag(a, dtype, st); return; }
-  if (use_conv3x3(a, dtype)) { launch_conv3x3(a, dtype, st); return; }
-  if (dtype == 0) launch_conv_t<float>(a, st);
-  else launch_conv_t<bf16_t>(a, st);
-}
-
-static bool wgrad_tiny_shape(const WgradArgs& a);
-static bool wgrad_tiny_shape_fwd(const WgradArgs& a) { return wgrad_tiny_shape(a); }
-// out_reduce2 (ConvArgs::pool2): only the narrow-layer 3x3 kernel pairs rows / columns of its output tile in registers
-bool conv_pool2_ok(const ConvArgs& a, int dtype) {
-  return !conv_few_ok(a) && !conv1x1_direct_ok(a, dtype) && !conv3x3_c1_ok(a) && use_conv3x3_small(a, dtype) && !(a.OH & 1) && !(a.OW & 1) &&
-         a.D1 == a.Cout && !a.bias && a.act == ACT_NONE;
-}
 // out_d2s (ConvArgs::d2s): the narrow-layer 3x3 kernel's D2S instantiation -- 16-bit activations, 64-byte source pixels (32 channels), 4 x 16 output
 // channels -- or the register-fed kernel's (whole 128-byte channel chunks, D1 a multiple of 32)
-static bool conv_d2s_small(const ConvArgs& a, int dtype) {
-  return dtype != 0 && a.C2 == 0 && a.C1 == 32 && a.Cout == 64 && a.D1 == 16 && conv3x3_small_ok(a, dtype);
+static bool conv_d2s_small(const ConvArgs& a, int dtype) { return dtype != 0 && a.C2 == 0 && a.C1 == 32 && a.Cout == 64 && a.D1 == 16 && conv3x3_small_ok(a, dtype); }
+
+// ---- the forward route: which kernel a descriptor runs on ----------------------------------------------------------------------------------------
+// conv_route is the ONLY place the order of the routes is written: launch_conv switches on it and every query below is "compute the route, look
+// up a property of it".  Several predicates read request pointers (skinny refuses stats / add1 / in_scale / bn_y, c1 refuses stats, stem and pw
+// refuse in_scale / bn_y), so a query routes the descriptor WITH the request it asks about, through a dummy non-null pointer (kAsked): right by
+// construction, where the hand-written chains were right only because the routes they left out happen to refuse the request.  "kept (n)" marks an
+// old answer that disagrees with launch_conv and stays as it was: DESIGN.md, "Kernel routes", finding n.
+enum class ConvRoute { S2d, D2sSmall, D2sFrag, Skinny, Stem, Few, Direct1x1, Pw, C1, Small3x3, Frag3x3, Patch3x3, Gemm };
+static float kAsked = 0.f;
+static ConvRoute conv_route(const ConvArgs& a, int dtype) {
+  if (a.s2d) return ConvRoute::S2d;      // (rd_api.cpp checked conv_s2d_ok)
+  if (a.d2s) return conv_d2s_small(a, dtype) ? ConvRoute::D2sSmall : ConvRoute::D2sFrag;      // (rd_api.cpp checked conv_d2s_ok)
+  if (conv_skinny_ok(a, dtype)) return ConvRoute::Skinny;
+  if (conv_stem_ok(a, dtype)) return ConvRoute::Stem;
+  if (conv_few_ok(a)) return ConvRoute::Few;
+  if (conv1x1_direct_ok(a, dtype)) return ConvRoute::Direct1x1;
+  if (conv_pw_ok(a, dtype)) return ConvRoute::Pw;
+  if (conv3x3_c1_ok(a)) return ConvRoute::C1;
+  if (use_conv3x3_small(a, dtype)) return ConvRoute::Small3x3;
+  if (use_conv3x3_frag(a, dtype)) return ConvRoute::Frag3x3;
+  if (use_conv3x3(a, dtype)) return ConvRoute::Patch3x3;
+  return ConvRoute::Gemm;
+}
+
+void launch_conv(const ConvArgs& a, int dtype, hipStream_t st) {
+  switch (conv_route(a, dtype)) {
+    case ConvRoute::S2d: case ConvRoute::D2sFrag: case ConvRoute::Frag3x3: launch_conv3x3_frag(a, dtype, st); return;
+    case ConvRoute::D2sSmall: case ConvRoute::Small3x3: launch_conv3x3_small(a, dtype, st); return;
+    case ConvRoute::Skinny: launch_linear_skinny(a, dtype, st); return;
+    case ConvRoute::Stem: launch_conv_stem(a, dtype, st); return;
+    case ConvRoute::Few: launch_conv_few(a, dtype, st); return;
+    case ConvRoute::Direct1x1: launch_conv1x1_direct(a, dtype, st); return;
+    case ConvRoute::Pw: launch_conv_pw(a, dtype, st); return;
+    case ConvRoute::C1: launch_conv3x3_c1(a, dtype, st); return;
+    case ConvRoute::Patch3x3: launch_conv3x3(a, dtype, st); return;
+    case ConvRoute::Gemm: if (dtype == 0) launch_conv_t<float>(a, st); else launch_conv_t<bf16_t>(a, st); return;
+  }
+}
+
+// statistics rows the routed kernel writes (persistent kernels: one row per block)
+int conv_stats_rows(const ConvArgs& a, int dtype) {
+  ConvArgs q = a; q.stats = &kAsked; q.s2d = 0;      // (kept (2): without the in_s2d flag)
+  ConvRoute r = conv_route(q, dtype);
+  if (r == ConvRoute::Pw && conv_route(a, dtype) == ConvRoute::Skinny) r = ConvRoute::Gemm;      // kept (1)
+  switch (r) {
+    case ConvRoute::D2sSmall: case ConvRoute::Small3x3: return conv3x3_small_blocks(q, dtype);
+    case ConvRoute::S2d: case ConvRoute::D2sFrag: case ConvRoute::Frag3x3: return conv3x3_frag_tiles(q, dtype);
+    case ConvRoute::Stem: return conv_stem_blocks(q);
+    case ConvRoute::Few: return conv_few_blocks(q);
+    case ConvRoute::Direct1x1: return conv1x1_direct_rows(q);
+    case ConvRoute::Pw: return conv_pw_rows(q);
+    case ConvRoute::Patch3x3: return conv3x3_tiles(q);
+    case ConvRoute::Skinny: case ConvRoute::C1: case ConvRoute::Gemm: break;      // (skinny and c1 refuse statistics: never routed here)
+  }
+  return (int)cdiv(a.M, 32 * conv_gemm_plan(q, dtype).wm);
+}
+// out_reduce2 (ConvArgs::pool2): only the narrow-layer 3x3 kernel pairs rows / columns of its output tile in registers
+bool conv_pool2_ok(const ConvArgs& a, int dtype) {
+  ConvArgs q = a; q.d2s = q.s2d = 0;      // (kept (2): this and the three fusion queries below answer for the layer without its out_d2s / in_s2d flag)
+  return conv_route(q, dtype) == ConvRoute::Small3x3 && !(a.OH & 1) && !(a.OW & 1) && a.D1 == a.Cout && !a.bias && a.act == ACT_NONE;
 }
 bool conv_d2s_ok(const ConvArgs& a, int dtype) {
   if (a.ups || a.pool2 || a.bias || a.act != ACT_NONE || a.in_scale || a.add1 || a.Cout != 4 * a.D1) return false;
@@ -1444,59 +1449,53 @@ bool conv_d2s_ok(const ConvArgs& a, int dtype) {
 // in_s2d (ConvArgs::s2d): the register-fed kernel's S2D instantiations
 bool conv_s2d_ok(const ConvArgs& a, int dtype) {
   if (a.ups || a.pool2 || a.d2s || a.bias || a.act != ACT_NONE || a.in_scale || a.add1 || a.C2 || a.D1 != a.Cout || a.stats) return false;
-  return conv3x3_frag_s2d_ok(a, dtype);
+  return conv3x3_frag_s2d_ok(a, dtype);      // (launch_conv sends an s2d descriptor straight to that kernel)
 }
 // ConvArgs::add1: the kernels that store through conv_epilogue_store except the narrow-layer one (not the few-channel / single-channel
-// streaming kernels, not the experimental LDS-DMA kernel), one destination, no 2x2 reduction
+// streaming kernels, whose variants sit at their register caps), one destination, no 2x2 reduction
 bool conv_add_ok(const ConvArgs& a, int dtype) {
-  if (a.D1 != a.Cout || a.pool2 || conv_few_ok(a)) return false;
-  if (conv1x1_direct_ok(a, dtype)) return true;
-  if (conv3x3_c1_ok(a) || use_conv3x3_small(a, dtype)) return false;      // (the narrow-layer variants sit at their register caps)
-  return true;
+  if (a.D1 != a.Cout || a.pool2) return false;
+  ConvArgs q = a; q.add1 = &kAsked;
+  const ConvRoute r = conv_route(q, dtype);
+  return r != ConvRoute::Few && r != ConvRoute::C1 && r != ConvRoute::Small3x3;
 }
 // ConvArgs::in_scale (consumer-side BatchNorm apply while staging): the two 3x3 / stride-1 kernels that stage whole 16-byte channel
 // vectors of a pixel patch through registers (every 3x3 layer of RC-Net that reads a BatchNorm-ed convolution's output)
 bool conv_in_affine_ok(const ConvArgs& a, int dtype) {
-  if (conv_few_ok(a) || conv1x1_direct_ok(a, dtype) || conv3x3_c1_ok(a)) return false;
-  return use_conv3x3_small(a, dtype) || use_conv3x3_frag(a, dtype);
+  ConvArgs q = a; q.d2s = q.s2d = 0; q.in_scale = &kAsked;
+  const ConvRoute r = conv_route(q, dtype);
+  return r == ConvRoute::Small3x3 || r == ConvRoute::Frag3x3;
 }
-// ConvArgs::bn_y (BatchNorm-backward sums in the data-gradient epilogue): kernels that store through conv_epilogue_store and write
-// statistics rows; dz = the first destination
+// ConvArgs::bn_y (BatchNorm-backward sums in the data-gradient epilogue): the register-fed 3x3 kernel (16x16x32 form) and the implicit-GEMM
+// kernel, which write one statistics row per tile through conv_epilogue_stats; dz must be whole 4-channel groups of the first destination, no
+// 2x2 reduction, no bias / activation of its own
 bool conv_bn_bwd_ok(const ConvArgs& a, int dtype) {
-  // the register-fed 3x3 kernel (16x16x32 form) and the implicit-GEMM kernel: both write one statistics row per tile through
-  // conv_epilogue_stats; dz must be whole 4-channel groups of the first destination, no 2x2 reduction, no bias / activation of its own
   if (a.pool2 || a.bias || a.act != ACT_NONE || (a.D1 & 3) || ((a.Cout - a.D1) & 3) || a.in_scale) return false;
-  if (conv_skinny_ok(a, dtype) || conv_stem_ok(a, dtype) || conv_few_ok(a) || conv1x1_direct_ok(a, dtype) || conv3x3_c1_ok(a) || use_conv3x3_small(a, dtype)) return false;
-  if (conv_pw_shape(a, dtype)) return false;      // (its epilogue takes the forward statistics only)
-  if (use_conv3x3_frag(a, dtype)) return !conv3x3_frag_is32(a, dtype);
-  if (use_conv3x3(a, dtype)) return false;      // (the patch-staged kernel is only a fallback since round 3)
-  return true;                                  // implicit GEMM
+  ConvArgs q = a; q.d2s = q.s2d = 0; q.bn_y = &kAsked;
+  const ConvRoute r = conv_route(q, dtype);
+  if (r == ConvRoute::Frag3x3) return !conv3x3_frag_is32(q, dtype);
+  q.bn_y = nullptr; q.stats = &kAsked;      // kept (3): refused where the pointwise kernel takes the layer WITHOUT the sums
+  return r == ConvRoute::Gemm && conv_route(q, dtype) != ConvRoute::Pw;      // (the patch-staged kernel is only a fallback since round 3)
 }
-bool wgrad_in_affine_ok(const WgradArgs& a, int dtype) { return !wgrad_tiny_shape_fwd(a) && wgrad3x3_tr_affine_ok(a, dtype); }
 // name of the kernel launch_conv picks for this shape (bench.py groups its per-launch timings by the names rocprofv3 reports)
 const char* conv_kernel_name(const ConvArgs& a, int dtype) {
-  if (conv_skinny_ok(a, dtype)) return dtype == 0 ? "linear_skinny_kernel<float>" : "linear_skinny_kernel<" RD_T16_NAME ">";
-  if (conv_stem_ok(a, dtype)) return "conv_stem_kernel";
-  if (conv_few_ok(a)) return "conv_few_kernel";
-  if (conv1x1_direct_ok(a, dtype)) return "conv1x1_direct_kernel";
-  if (conv_pw_ok(a, dtype)) return conv_pw_name(a, dtype);
-  if (conv3x3_c1_ok(a)) return "conv3x3_c1_kernel";
-  if (a.s2d) return conv3x3_frag_name(a, dtype);
-  if (a.d2s) return conv_d2s_small(a, dtype) ? conv3x3_small_name(a, dtype) : conv3x3_frag_name(a, dtype);
-  if (use_conv3x3_small(a, dtype)) return conv3x3_small_name(a, dtype);
-  if (use_conv3x3_frag(a, dtype)) return conv3x3_frag_name(a, dtype);
-  if (use_conv3x3(a, dtype)) return conv3x3_patch_name(a, dtype);
-  {     // the implicit-GEMM kernel's instantiation, as launch_conv_t picks it
-    static thread_local char buf[96];
-    const int ve = dtype == 0 ? 4 : 8, Cin = a.C1 + a.C2, es = dtype == 0 ? 4 : 2;
-    const bool vec = (Cin % ve == 0) && (a.C1 % ve == 0);
-    int bn, wm;
-    conv_tiles(a.M, a.Cout, bn, wm);
-    const bool deep = conv_gemm_deep(a, dtype), par = conv_gemm_par(a, dtype);
-    (void)es;
-    snprintf(buf, sizeof(buf), "conv_gemm_kernel<%s, %d, %s, %d, %s, %s>", dtype == 0 ? "float" : RD_T16_NAME, bn, vec ? "true" : "false", wm, deep ? "true" : "false", par ? "true" : "false");
-    return buf;
+  switch (conv_route(a, dtype)) {
+    case ConvRoute::S2d: case ConvRoute::D2sFrag: case ConvRoute::Frag3x3: return conv3x3_frag_name(a, dtype);      // ("" where that kernel has no plan: finding 4)
+    case ConvRoute::D2sSmall: case ConvRoute::Small3x3: return conv3x3_small_name(a, dtype);
+    case ConvRoute::Skinny: return dtype == 0 ? "linear_skinny_kernel<float>" : "linear_skinny_kernel<" RD_T16_NAME ">";
+    case ConvRoute::Stem: return "conv_stem_kernel";
+    case ConvRoute::Few: return "conv_few_kernel";
+    case ConvRoute::Direct1x1: return "conv1x1_direct_kernel";
+    case ConvRoute::Pw: return conv_pw_name(a, dtype);
+    case ConvRoute::C1: return "conv3x3_c1_kernel";
+    case ConvRoute::Patch3x3: return conv3x3_patch_name(a, dtype);
+    case ConvRoute::Gemm: break;
   }
+  static thread_local char buf[96];
+  const GemmPlan p = conv_gemm_plan(a, dtype);
+  snprintf(buf, sizeof(buf), "conv_gemm_kernel<%s, %d, %s, %d, %s, %s>", dtype == 0 ? "float" : RD_T16_NAME, p.bn, p.vec ? "true" : "false", p.wm,
+           p.deep ? "true" : "false", p.par ? "true" : "false");
+  return buf;
 }
 void launch_pack_weights(const float* w, void* out, int Cout, int Cin, int KH, int KW, int mode, int dtype,
                          hipStream_t st, int CinSrc) {
@@ -1531,12 +1530,7 @@ void launch_pack_weights_batch(const void* items, int n, hipStream_t st) {
 }
 
 // split the pixel reduction so the launch has a few blocks per CU, stage-aligned
-int wgrad_nsplit(int M, int K, int Cout);
-int wgrad_slabs(int M, int K, int Cout) {
-  int ns = wgrad_nsplit(M, K, Cout);
-  return (Cout <= 32 && K <= 9 * 64) ? std::max(ns, HALO_BLOCKS) : ns;  // the halo-tile path writes one slab per persistent block
-}
-int wgrad_nsplit(int M, int K, int Cout) {
+static int wgrad_nsplit(int M, int K, int Cout) {
   int cot = pick_bn(Cout);
   int64_t tiles = cdiv(K, 128) * cdiv(Cout, cot);
   const int target = rd_opt(OPT_WGRAD_BLOCKS, 1024);   // experiment hook (rd_set_option)
@@ -1545,6 +1539,10 @@ int wgrad_nsplit(int M, int K, int Cout) {
   int64_t s = std::max<int64_t>(1, std::min(want, maxs));
   if (s >= 8) s -= s % 8;   // XCD x owns the splits x, x+8, ...: a multiple of 8 keeps the XCDs balanced
   return (int)s;
+}
+static int wgrad_slabs(int M, int K, int Cout) {
+  int ns = wgrad_nsplit(M, K, Cout);
+  return (Cout <= 32 && K <= 9 * 64) ? std::max(ns, HALO_BLOCKS) : ns;  // the halo-tile path writes one slab per persistent block
 }
 
 template <typename T>
@@ -1640,7 +1638,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_tiny_kernel(WgradArgs a) {
       a.slab[((int64_t)blockIdx.x * a.Cout + co0 + e) * K + k] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
   }
 }
-// -> number of slabs written (0: shape not handled here)
 static bool wgrad_tiny_shape(const WgradArgs& a) {
   const int min_m = rd_opt(OPT_WGRAD_TINY_MIN_M, 1 << 16);      // test hook (rd_set_option): 0 sends small cases through this kernel
   if (a.ups || a.C2 || a.KH != a.KW || a.M < min_m || wgrad_slabs(a.M, a.K, a.Cout) < HALO_BLOCKS) return false;
@@ -1648,17 +1645,15 @@ static bool wgrad_tiny_shape(const WgradArgs& a) {
   // group re-reads the 27-tap patch -- so it stays there)
   return (a.KH == 3 && a.C1 == 3 && a.stride == 1 && a.Cout <= 4) || (a.KH == 1 && a.C1 == 32 && a.stride == 1 && a.Cout == 1);
 }
-bool wgrad_streams(const WgradArgs& a) { return wgrad_tiny_shape(a); }
+// -> number of slabs written (wgrad_route checked wgrad_tiny_shape)
 template <typename T>
 static int launch_wgrad_tiny(const WgradArgs& a, hipStream_t st) {
-  if (!wgrad_tiny_shape(a)) return 0;
   const int nblk = (int)std::min<int64_t>(HALO_BLOCKS, cdiv(a.M, 256 * 4));      // the workspace holds >= HALO_BLOCKS slabs for these shapes
 #define RD_TINY(KHV, CINV, GV, SV) { dim3 grid((unsigned)nblk, (unsigned)cdiv(a.Cout, GV));                                       \
     hipLaunchKernelGGL((conv_wgrad_tiny_kernel<T, KHV, CINV, GV, SV>), grid, dim3(256), 0, st, a); return nblk; }
   if (a.KH == 3 && a.C1 == 3 && a.stride == 1 && a.Cout <= 4) { if (a.Cout <= 3) RD_TINY(3, 3, 3, 1) else RD_TINY(3, 3, 4, 1) }
-  if (a.KH == 1 && a.C1 == 32 && a.stride == 1 && a.Cout == 1) RD_TINY(1, 32, 1, 1)
+  RD_TINY(1, 32, 1, 1)      // (a.KH == 1 && a.C1 == 32 && a.Cout == 1)
 #undef RD_TINY
-  return 0;
 }
 
 void launch_wgrad_reduce_batch(const WgradReduceItem* items, int n, hipStream_t st) {
@@ -1677,6 +1672,30 @@ void launch_wgrad_reduce_batch(const WgradReduceItem* items, int n, hipStream_t 
   }
 }
 
+// ---- the weight-gradient route (the forward's conv_route over again: one order, every query looks a property of the route up) -----------------
+// conv_wgrad_bf16_kernel: whole 16-byte vectors of 16-bit channels on all three axes
+static bool wgrad_bf16_mfma_ok(const WgradArgs& a, int dtype) { return dtype == 1 && ((a.C1 + a.C2) % 8 == 0) && (a.C1 % 8 == 0) && (a.Cout % 8 == 0); }
+enum class WgradRoute { Tiny, Tr3x3, Halo, Bf16Mfma, Generic };
+static WgradRoute wgrad_route(const WgradArgs& a, int dtype) {
+  if (wgrad_tiny_shape(a)) return WgradRoute::Tiny;                  // few channels, millions of pixels: register-accumulating streaming kernel
+  if (wgrad3x3_tr_ok(a, dtype)) return WgradRoute::Tr3x3;            // bf16 3x3 layers: transpose-read kernels, one slab per persistent block (<= HALO_BLOCKS)
+  if (wgrad_halo_ok(a, dtype)) return WgradRoute::Halo;
+  if (wgrad_bf16_mfma_ok(a, dtype)) return WgradRoute::Bf16Mfma;
+  return WgradRoute::Generic;
+}
+bool wgrad_streams(const WgradArgs& a, int dtype) { return wgrad_route(a, dtype) == WgradRoute::Tiny; }
+// WgradArgs::in_scale (consumer-side BatchNorm apply): the 8 x TW transpose-read kernel only -- routed WITH the request, as the forward queries are
+bool wgrad_in_affine_ok(WgradArgs a, int dtype) { a.in_scale = &kAsked; return wgrad_route(a, dtype) == WgradRoute::Tr3x3; }
+// slabs the caller's workspace must hold: the split / halo / tiny count of the shape, and the persistent blocks of the transpose-read kernels.  The
+// plain and the consumer-side-affine launch of one shape may pick different transpose-read kernels (map-fitted / 8 x TW): the larger of the two.
+int wgrad_workspace_slabs(WgradArgs a, int dtype) {
+  int ns = wgrad_slabs(a.M, a.K, a.Cout);
+  if (wgrad_route(a, dtype) == WgradRoute::Tr3x3) ns = std::max(ns, wgrad3x3_tr_blocks(a));
+  a.in_scale = &kAsked;
+  if (wgrad_route(a, dtype) == WgradRoute::Tr3x3) ns = std::max(ns, wgrad3x3_tr_blocks(a));
+  return ns;
+}
+
 // defer != nullptr: the partial slabs are produced, the reduction into dw is left to a later launch_wgrad_reduce_batch over *defer
 void launch_wgrad(WgradArgs a, int dtype, float* dw, int accumulate, hipStream_t st, WgradReduceItem* defer) {
   const int Cin = a.C1 + a.C2;
@@ -1685,56 +1704,49 @@ void launch_wgrad(WgradArgs a, int dtype, float* dw, int accumulate, hipStream_t
                  defer->nsplit = nsplit; defer->accumulate = accumulate; }
     else launch_wgrad_reduce(a.slab, dw, a.Cout, Cin, a.KH, a.KW, nsplit, accumulate, st);
   };
-  if (wgrad_tiny_shape(a)) {      // few channels, millions of pixels: register-accumulating streaming kernel
-    const int ns = dtype == 0 ? launch_wgrad_tiny<float>(a, st) : launch_wgrad_tiny<bf16_t>(a, st);
-    if (ns) { reduce(ns); return; }
-  }
-  if (wgrad3x3_tr_ok(a, dtype)) {  // bf16 narrow layers: transpose-read kernel, one slab per persistent block (<= HALO_BLOCKS)
-    launch_wgrad3x3_tr(a, st);
-    reduce(wgrad3x3_tr_blocks(a));
-    return;
-  }
-  if (wgrad_halo_ok(a, dtype)) {
-    int TH, TW;
-    halo_geom(Cin, a.Cout, TH, TW);
-    int64_t ntiles = (int64_t)a.N * cdiv(a.OH, TH) * cdiv(a.OW, TW);
-    int nblk = (int)std::min<int64_t>(ntiles, HALO_BLOCKS);
-    if (dtype == 0) launch_wgrad_halo_t<float>(a, nblk, st);
-    else launch_wgrad_halo_t<bf16_t>(a, nblk, st);
-    reduce(nblk);
-    return;
-  }
-  a.nsplit = wgrad_nsplit(a.M, a.K, a.Cout);
-  a.rows_per_split = (int)(cdiv(cdiv(a.M, a.nsplit), 32) * 32);
-  a.nsplit = (int)cdiv(a.M, a.rows_per_split);
-  bool vec = (Cin % 4 == 0) && (a.C1 % 4 == 0);
-  if (dtype == 1 && (Cin % 8 == 0) && (a.C1 % 8 == 0) && (a.Cout % 8 == 0)) {
-    // bf16 MFMA path: 64-pixel stages
-    a.rows_per_split = (int)(cdiv(cdiv(a.M, wgrad_nsplit(a.M, a.K, a.Cout)), 64) * 64);
+  auto split = [&](int stage) {      // split-K kernels: stage-aligned pixel ranges (32-pixel stages, 64 on the bf16 MFMA)
+    a.rows_per_split = (int)(cdiv(cdiv(a.M, wgrad_nsplit(a.M, a.K, a.Cout)), stage) * stage);
     a.nsplit = (int)cdiv(a.M, a.rows_per_split);
-    int cot = pick_bn(a.Cout);
-    dim3 grid(wg_grid(a.K, a.Cout, cot, a.nsplit));
-    if (cot == 16) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<16>), grid, dim3(256), 0, st, a);
-    else if (cot == 32) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<32>), grid, dim3(256), 0, st, a);
-    else if (cot == 64) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<64>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_wgrad_bf16_kernel<128>), grid, dim3(256), 0, st, a);
-    reduce(a.nsplit);
-    return;
+  };
+  switch (wgrad_route(a, dtype)) {
+    case WgradRoute::Tiny: reduce(dtype == 0 ? launch_wgrad_tiny<float>(a, st) : launch_wgrad_tiny<bf16_t>(a, st)); return;
+    case WgradRoute::Tr3x3: launch_wgrad3x3_tr(a, st); reduce(wgrad3x3_tr_blocks(a)); return;
+    case WgradRoute::Halo: {
+      int TH, TW; halo_geom(Cin, a.Cout, TH, TW);
+      const int nblk = (int)std::min<int64_t>((int64_t)a.N * cdiv(a.OH, TH) * cdiv(a.OW, TW), HALO_BLOCKS);
+      if (dtype == 0) launch_wgrad_halo_t<float>(a, nblk, st); else launch_wgrad_halo_t<bf16_t>(a, nblk, st);
+      reduce(nblk);
+      return;
+    }
+    case WgradRoute::Bf16Mfma: {
+      split(64);
+      const int cot = pick_bn(a.Cout);
+      const dim3 grid(wg_grid(a.K, a.Cout, cot, a.nsplit));
+      if (cot == 16) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<16>), grid, dim3(256), 0, st, a);
+      else if (cot == 32) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<32>), grid, dim3(256), 0, st, a);
+      else if (cot == 64) hipLaunchKernelGGL((conv_wgrad_bf16_kernel<64>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((conv_wgrad_bf16_kernel<128>), grid, dim3(256), 0, st, a);
+      reduce(a.nsplit);
+      return;
+    }
+    case WgradRoute::Generic: {
+      split(32);
+      const bool vec = (Cin % 4 == 0) && (a.C1 % 4 == 0);
+      if (dtype == 0) launch_wgrad_t<float>(a, vec, st); else launch_wgrad_t<bf16_t>(a, vec, st);
+      reduce(a.nsplit);
+      return;
+    }
   }
-  if (dtype == 0) launch_wgrad_t<float>(a, vec, st);
-  else launch_wgrad_t<bf16_t>(a, vec, st);
-  reduce(a.nsplit);
 }
 
 const char* wgrad_kernel_name(const WgradArgs& a, int dtype) {
-  const int Cin = a.C1 + a.C2;
-  if (wgrad_tiny_shape(a)) return "conv_wgrad_tiny_kernel";
-  if (wgrad3x3_tr_ok(a, dtype)) return wgrad3x3_tr_name(a);
-  if (wgrad_halo_ok(a, dtype)) return "conv_wgrad_halo_kernel";
-  if (dtype == 1 && (Cin % 8 == 0) && (a.C1 % 8 == 0) && (a.Cout % 8 == 0)) {
-    static thread_local char buf[48];
-    snprintf(buf, sizeof(buf), "conv_wgrad_bf16_kernel<%d>", pick_bn(a.Cout));
-    return buf;
+  static thread_local char buf[48];
+  switch (wgrad_route(a, dtype)) {
+    case WgradRoute::Tiny: return "conv_wgrad_tiny_kernel";
+    case WgradRoute::Tr3x3: return wgrad3x3_tr_name(a);
+    case WgradRoute::Halo: return "conv_wgrad_halo_kernel";
+    case WgradRoute::Bf16Mfma: snprintf(buf, sizeof(buf), "conv_wgrad_bf16_kernel<%d>", pick_bn(a.Cout)); return buf;
+    case WgradRoute::Generic: break;
   }
   return "conv_wgrad_kernel";
 }

@@ -639,7 +639,8 @@ int conv3x3_frag_blocks(const ConvArgs& a, int dtype) { FragPlan p; frag_plan(a,
 // the name rocprofv3 prints for the instantiation this shape runs on (dtype tag as in the kernel-trace CSV)
 const char* conv3x3_frag_name(const ConvArgs& a, int dtype) {
   static thread_local char buf[96];
-  FragPlan p; frag_plan(a, dtype, p);
+  FragPlan p;
+  if (!frag_plan(a, dtype, p)) return "";      // (an out_d2s / in_s2d descriptor this kernel has no plan for: rd_conv_fwd refuses it)
   static const int npt[] = {8, 4, 4, 8, 4, 4, 8}, wpx[] = {1, 2, 2, 2, 4, 4, 4}, wch[] = {4, 4, 2, 2, 2, 1, 1};
   const bool multi = (a.C1 + a.C2) * (dtype == 0 ? 4 : 2) > STAGE_BYTES;
   if (p.v32) {

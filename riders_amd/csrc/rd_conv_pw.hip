@@ -224,7 +224,7 @@ __global__ __launch_bounds__(64 * KS * NT) void pw_gemm_kernel(ConvArgs a, int m
 // bound).  Default: those shapes only; "pw_min_m" = 0 (tests) sends every eligible pointwise layer here, "pw_ks" forces a block shape.
 static int pw_min_m() { return rd_opt(OPT_PW_MIN_M, -1); }      // test hook (rd_set_option "pw_min_m": 0 forces, 1 << 30 disables)
 // the shape alone (ConvArgs::bn_y / add1 / stats are per call)
-bool conv_pw_shape(const ConvArgs& a, int dtype) {
+static bool conv_pw_shape(const ConvArgs& a, int dtype) {
   const int ve = dtype == 0 ? 4 : 8;
   const bool form = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.dil == 1 && a.C2 == 0 && !a.ups && a.OH == a.Hin && a.OW == a.Win &&
                     a.K == a.C1 && (a.C1 % ve) == 0 && (a.Cout % 8) == 0 && a.D1 == a.Cout && !a.pool2 && !a.d2s && !a.s2d && a.M <= 16384;

@@ -7,9 +7,6 @@ using namespace rdt;
 int conv_rows_pad(int rows);
 int conv_kpad(int K, int dtype);
 int64_t conv_packed_elems(int rows, int K, int dtype);
-int conv_block_pixels(int M, int Cout);
-int wgrad_nsplit(int M, int K, int Cout);
-int wgrad_slabs(int M, int K, int Cout);
 int conv_stats_rows(const ConvArgs& a, int dtype);
 void launch_conv(const ConvArgs& a, int dtype, hipStream_t st);
 const char* conv_kernel_name(const ConvArgs& a, int dtype);
@@ -19,8 +16,14 @@ bool conv_s2d_ok(const ConvArgs& a, int dtype);
 bool conv_add_ok(const ConvArgs& a, int dtype);
 bool conv_in_affine_ok(const ConvArgs& a, int dtype);
 bool conv_bn_bwd_ok(const ConvArgs& a, int dtype);
-bool wgrad_in_affine_ok(const WgradArgs& a, int dtype);
+bool wgrad_in_affine_ok(WgradArgs a, int dtype);
+int wgrad_workspace_slabs(WgradArgs a, int dtype);
 const char* wgrad_kernel_name(const WgradArgs& a, int dtype);
+// rd_conv_pw.hip: pointwise layers on a few thousand pixels
+bool conv_pw_ok(const ConvArgs& a, int dtype);
+int conv_pw_rows(const ConvArgs& a);
+const char* conv_pw_name(const ConvArgs& a, int dtype);
+void launch_conv_pw(const ConvArgs& a, int dtype, hipStream_t st);
 // rd_conv3x3.hip
 bool conv3x3_ok(const ConvArgs& a, int dtype);
 int conv3x3_tiles(const ConvArgs& a);
@@ -50,12 +53,11 @@ void launch_conv3x3_c1(const ConvArgs& a, int dtype, hipStream_t st);
 void launch_pack_weights(const float* w, void* out, int Cout, int Cin, int KH, int KW, int mode, int dtype, hipStream_t st, int CinSrc = 0);
 void launch_pack_weights_batch(const void* items, int n, hipStream_t st);
 void launch_wgrad(WgradArgs a, int dtype, float* dw, int accumulate, hipStream_t st, WgradReduceItem* defer);
-bool wgrad_streams(const WgradArgs& a);
+bool wgrad_streams(const WgradArgs& a, int dtype);
 void launch_wgrad_reduce_batch(const WgradReduceItem* items, int n, hipStream_t st);
 
 // rd_wgrad3x3.hip
 bool wgrad3x3_tr_ok(const WgradArgs& a, int dtype);
-bool wgrad3x3_tr_affine_ok(const WgradArgs& a, int dtype);
 int wgrad3x3_tr_blocks(const WgradArgs& a);
 void launch_wgrad3x3_tr(const WgradArgs& a, hipStream_t st);
 const char* wgrad3x3_tr_name(const WgradArgs& a);

@@ -589,6 +589,7 @@ static int fit_blocks(const WgradArgs& a, const FitPlan& p) {
   else cap = (int)std::max<int64_t>(1, std::min<int64_t>(cap, ntiles / 32));      // >= 4 tiles per block: every block writes a slab slice
   return 8 * (int)std::min<int64_t>(cdiv(ntiles, 8), cap);
 }
+// (with WgradArgs::in_scale set the fitted kernel, which has no affine form, is out and the 8 x TW kernel must take the shape)
 bool wgrad3x3_tr_ok(const WgradArgs& a, int dtype) {
   { FitPlan fp; if (fit_plan(a, dtype, fp)) return true; }
   if (dtype != 1 || !tr_geom(a)) return false;
@@ -599,15 +600,6 @@ bool wgrad3x3_tr_ok(const WgradArgs& a, int dtype) {
   const int tw = tr_tw(a);
   const double eff = (double)a.OH * a.OW / (double)(cdiv(a.OH, 8) * 8 * cdiv(a.OW, tw) * tw);
   return eff >= 0.6;
-}
-bool wgrad3x3_tr_affine_ok(const WgradArgs& a, int dtype) {      // (asked WITHOUT in_scale set: the fitted kernel has no affine form, the 8 x TW kernel must take the shape)
-  if (dtype != 1 || !tr_geom(a)) return false;
-  if ((int64_t)a.N * a.Hin * a.Win >= (int64_t)1 << 31) return false;
-  if (tr_narrow(a)) return true;
-  const int Cin = a.C1 + a.C2;
-  if (Cin % 64 != 0 || a.Cout % 8 != 0) return false;
-  const int tw = tr_tw(a);
-  return (double)a.OH * a.OW / (double)(cdiv(a.OH, 8) * 8 * cdiv(a.OW, tw) * tw) >= 0.6;
 }
 static void tr_slices(const WgradArgs& a, int& cti, int& rt, int& nci, int& nco) {
   const int Cin = a.C1 + a.C2;
