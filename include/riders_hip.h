@@ -253,13 +253,18 @@ int32_t rd_affine_act_add_ok(int32_t C, int32_t dtype);
 int rd_affine_act_add(const void* y, const float* scale, const float* shift, int32_t act1, float slope1, const void* residual, void* out,
                       int64_t pixels, int32_t C, int32_t act2, float slope2, int32_t dtype, void* stream);
 int32_t rd_bn_bwd_rows(int64_t pixels, int32_t C);
+/* 1 when the backward kernels of this channel count recompute the activation's argument from y (the 16-byte-vector forms: whole vectors, at
+   most 256 of them); 0: the scalar kernels, which read z -- rd_bn_act_bwd_recompute then needs z and rd_bn_act_bwd_from_partial refuses an
+   activation.  Callers ask before they decide not to keep z. */
+int32_t rd_bn_bwd_recompute_ok(int32_t C, int32_t dtype);
 /* full BN(+act) backward: dy = dBN(dz * act'(z)); dres (optional) = dz * act'(z); dgamma/dbeta fp32 */
 int rd_bn_act_bwd(const void* dz, const void* z, const void* y, const float* save_mean, const float* save_rstd,
                   const float* scale, float* partial /* [rows][C][2] */, float* coef /* [2][C] */, float* dgamma,
                   float* dbeta, int32_t accumulate, void* dy, void* dres, int64_t pixels, int32_t C, int32_t act,
                   float slope, int32_t dtype, void* stream);
 /* same, for z = act(scale*y + shift) WITHOUT a residual: the activation's argument is recomputed from y (bit-identical to the forward's
-   expression), so z is not read (one tensor less in both passes); z is only consulted when C is not a multiple of the 16-byte vector */
+   expression), so z is not read (one tensor less in both passes); z is only consulted -- and must then be given, unless act is none -- where
+   the channel count has no 16-byte-vector kernel: not a multiple of the vector, or more than 256 vectors (1024 fp32 / 2048 16-bit channels) */
 int rd_bn_act_bwd_recompute(const void* dz, const void* z, const void* y, const float* save_mean, const float* save_rstd,
                             const float* scale, const float* shift, float* partial, float* coef, float* dgamma, float* dbeta,
                             int32_t accumulate, void* dy, void* dres, int64_t pixels, int32_t C, int32_t act, float slope,
@@ -272,7 +277,8 @@ int rd_bn_act_bwd_recompute_phases(const void* dz, const void* z, const void* y,
                                    int32_t dtype, int32_t phases, void* stream);
 /* The same backward when the reduce pass has already been done elsewhere: `partial` = rows x row_channels x (sum g, sum g * xhat) written by
  * the data gradient that produced dz (rd_conv_fwd_fused with rd_conv_fusion.bn_y: the statistics rows of that launch, rd_conv_stats_rows of
- * ITS descriptor, row_channels = its Cout >= C).  Finalize + apply only: dz and y are read once. */
+ * ITS descriptor, row_channels = its Cout >= C).  Finalize + apply only: dz and y are read once.  There is no z to fall back on: with an
+ * activation, channel counts without a 16-byte-vector kernel (see rd_bn_act_bwd_recompute) are refused. */
 int rd_bn_act_bwd_from_partial(const void* dz, const void* y, const float* mean, const float* rstd, const float* scale, const float* shift,
                                const float* partial, int32_t rows, int32_t row_channels, float* coef, float* dgamma, float* dbeta, int32_t accumulate,
                                void* dy, int64_t pixels, int32_t C, int32_t act, float slope, int32_t dtype, void* stream);

@@ -464,6 +464,7 @@ const char* rd_bn_slab_kernel_name(int32_t which, int64_t pixels, int32_t dtype,
   return RD_NS(dtype, bn_slab_kernel_name)(which, pixels, RD_DT(dtype), act);
 }
 int32_t rd_bn_bwd_rows(int64_t pixels, int32_t C) { return rd::bn_bwd_rows(pixels, C); }
+int32_t rd_bn_bwd_recompute_ok(int32_t C, int32_t dtype) { return dt_ok(dtype) && C > 0 && rd::bn_bwd_recomputes(C, RD_DT(dtype)) ? 1 : 0; }
 int rd_bn_act_bwd(const void* dz, const void* z, const void* y, const float* mean, const float* rstd, const float* scale,
                   float* partial, float* coef, float* dgamma, float* dbeta, int32_t accumulate, void* dy, void* dres,
                   int64_t pixels, int32_t C, int32_t act, float slope, int32_t dtype, void* stream) {
@@ -479,7 +480,7 @@ int rd_bn_act_bwd_recompute_phases(const void* dz, const void* z, const void* y,
                                    const float* shift, float* partial, float* coef, float* dgamma, float* dbeta, int32_t accumulate, void* dy,
                                    void* dres, int64_t pixels, int32_t C, int32_t act, float slope, int32_t dtype, int32_t phases, void* stream) {
   if (!dz || !y || !mean || !rstd || !scale || !shift || !partial || !coef || !dy || !dt_ok(dtype)) return fail("bn_act_bwd_recompute: bad args");
-  if (act != RD_ACT_NONE && !z && (C % (dtype == RD_F32 ? 4 : 8))) return fail("bn_act_bwd_recompute: this channel count needs z");
+  if (act != RD_ACT_NONE && !z && !rd::bn_bwd_recomputes(C, RD_DT(dtype))) return fail("bn_act_bwd_recompute: this channel count needs z");
   int rows = rd::bn_bwd_rows(pixels, C);
   if (phases & 1) RD_NS(dtype, launch_bn_bwd_reduce)(dz, z, y, mean, rstd, partial, pixels, C, act, slope, RD_DT(dtype), S(stream), scale, shift);
   if (phases & 2) rd::launch_bn_bwd_finalize(partial, rows, C, (double)pixels, dgamma, dbeta, accumulate, coef, coef + C, S(stream));
@@ -491,7 +492,7 @@ int rd_bn_act_bwd_from_partial(const void* dz, const void* y, const float* mean,
                                void* dy, int64_t pixels, int32_t C, int32_t act, float slope, int32_t dtype, void* stream) {
   if (!dz || !y || !mean || !rstd || !scale || !shift || !partial || !coef || !dy || !dt_ok(dtype)) return fail("bn_act_bwd_from_partial: bad args");
   if (rows <= 0 || row_channels < C || C <= 0) return fail("bn_act_bwd_from_partial: bad partial geometry (rows %d, row channels %d, C %d)", rows, row_channels, C);
-  if (act != RD_ACT_NONE && (C % (dtype == RD_F32 ? 4 : 8))) return fail("bn_act_bwd_from_partial: this channel count needs z");
+  if (act != RD_ACT_NONE && !rd::bn_bwd_recomputes(C, RD_DT(dtype))) return fail("bn_act_bwd_from_partial: this channel count needs z");
   rd::launch_bn_bwd_finalize(partial, rows, C, (double)pixels, dgamma, dbeta, accumulate, coef, coef + C, S(stream), row_channels);
   RD_NS(dtype, launch_bn_bwd_apply)(dz, nullptr, y, mean, rstd, scale, coef, coef + C, dy, nullptr, pixels, C, act, slope, RD_DT(dtype), S(stream), shift);
   return done("rd_bn_act_bwd_from_partial");

@@ -78,6 +78,7 @@ void launch_bn_finalize(const float* partial, int rows, int C, double count, con
 void launch_affine_act(const void* y, const float* scale, const float* shift, const void* res, void* out, int64_t pixels,
                        int C, int act, float slope, int dtype, hipStream_t st);
 bool affine_act_add_ok(int C, int dtype);
+bool bn_bwd_recomputes(int C, int dtype);
 void launch_affine_act_add(const void* y, const float* scale, const float* shift, int act1, float slope1, const void* res, void* out,
                            int64_t pixels, int C, int act2, float slope2, int dtype, hipStream_t st);
 const char* bn_kernel_name(int which, int C, int dtype, int act, int flag);

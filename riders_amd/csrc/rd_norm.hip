@@ -756,6 +756,8 @@ void launch_affine_act(const void* y, const float* scale, const float* shift, co
 }
 
 bool affine_act_add_ok(int C, int dtype) { return vec_ok(C, dtype); }
+// the backward kernels that recompute the activation's argument from y (the vec and gen forms); the scalar fall-back reads z
+bool bn_bwd_recomputes(int C, int dtype) { return vec_ok(C, dtype) || gen_ok(C, dtype); }
 void launch_affine_act_add(const void* y, const float* scale, const float* shift, int act1, float slope1, const void* res, void* out,
                            int64_t pixels, int C, int act2, float slope2, int dtype, hipStream_t st) {
   const int64_t nvec = pixels * C / (dtype == 0 ? 4 : 8);

@@ -283,6 +283,12 @@ def _bn_finalize_apply(stats, y, bn, coef, z, pixels, C, act, slope, dt, st):
                "bn finalize+apply+act M=%d C=%d [one launch]" % (pixels, C), kernel=lambda: lib.rd_bn_slab_kernel_name(0, pixels, dt, act).decode())
 
 
+def _bn_recomputes(C, dt):
+    """the BatchNorm backward of this channel count has a kernel that recomputes the activation's argument from y (the library's answer:
+    rd_bn_bwd_recompute_ok); wider or ragged layers take the scalar kernels, which read z, so their z has to be kept"""
+    return bool(L().rd_bn_bwd_recompute_ok(C, dt))
+
+
 def _bn_bwd_recompute(dz, z, y, mean, rstd, scale, shift, partial, coef2, dgam, dbet, acc, dy, dres, pixels, C, act, slope, dt, st, nbytes, desc):
     """rd_bn_act_bwd_recompute; under a kernel timer its reduce / finalize / apply launches are issued (and timed, and named) one by one so
     that bench.py's roofline can rank the BatchNorm passes next to the convolution kernels."""
@@ -1347,7 +1353,7 @@ def _conv_plan(lib, x, x2, weight, bias, stride, pad, up, bn, act, slope, residu
         # (layers the streaming few-channel kernels take -- SML's 3 -> 3 `first` convolution -- are handed over as they are; an input that
         # needs a gradient -- the SML backbone's stem behind `first` -- gets it from the un-padded descriptor in _conv_bwd_data)
         p.C1 = p.cin_pad = (p.C1 + p.ve - 1) // p.ve * p.ve
-    p.lazy = bool(lazy_out and p.use_bn and residual is None and _state["lazy_bn"] >= int(lazy_out) and _state["bn_recompute"] and p.Cout % p.ve == 0)
+    p.lazy = bool(lazy_out and p.use_bn and residual is None and _state["lazy_bn"] >= int(lazy_out) and _state["bn_recompute"] and _bn_recomputes(p.Cout, p.dt))
     p.pixels = p.N * p.OH * p.OW
     p.flops = 2.0 * p.pixels * p.Cout * p.KH * p.KW * p.Cin  # algorithmic (2 FLOP per MAC), same count for dgrad / wgrad
     p.shp = "M=%d Cin=%d Cout=%d k=%d s=%d%s" % (p.pixels, p.Cin, p.Cout, p.KH, stride, " up" if p.is_up else "")
@@ -1649,7 +1655,7 @@ def conv_block(x, weight, *, x2=None, bias=None, stride=1, pad=None, up=None, bn
     if not (p.need_in or p.need_res or p.w_req or (p.use_bn and bn.weight is not None and bn.weight.requires_grad)):
         return zk
     t.mark(zk)
-    if p.bn_train and residual is None and _state["bn_recompute"] and _state["bn_bwd_fused"] and p.Cout % p.ve == 0:
+    if p.bn_train and residual is None and _state["bn_recompute"] and _state["bn_bwd_fused"] and _bn_recomputes(p.Cout, p.dt):
         t.bn_src[id(zk)] = dict(y=y, coef=coef, act=act, slope=slope, C=p.Cout, partial=None)
     s = _Plan(x=x, x_real=x_real, x2=x2, xk=xk, lz=lz, y=y, z=z, coef=coef, bn=bn, weight=weight, residual=residual)      # what the backward keeps alive
 

@@ -2573,6 +2573,11 @@ ROUTE_CASES = [
     dict(name="bn_slab_lazy_out", inputs={"x": ((2, 8, 5, 4), True)},
          layers=[_rl("conv", "x", "h", 8, 256, k=1, bn="train", act="relu6", lazy_out=2), _rl("conv", "h", "y", 256, 8, k=1)], outs=["y"], switches={"lazy_bn": 2},
          calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_act_bwd_slab", "rd_conv_pack_weights", "rd_conv_fwd", "rd_linear_wgrad_batch"]),
+    # more than 256 channel vectors: the backward takes the scalar kernels, which read z -- the layer must not go lazy, and z is handed over
+    dict(name="bn_wide_not_lazy", force=lambda: _route_opts(bn_slab=0), inputs={"x": ((2, 8, 5, 4), True)},
+         layers=[_rl("conv", "x", "h", 8, 1028, k=1, bn="train", act="relu6", lazy_out=2), _rl("conv", "h", "y", 1028, 8, k=1)], outs=["y"], switches={"lazy_bn": 2},
+         counts=dict(materialized=0),
+         calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act", "rd_conv_pack_weights", "rd_conv_fwd", "rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_act_bwd_recompute", "rd_conv_pack_weights", "rd_conv_fwd", "rd_linear_wgrad_batch"]),
     dict(name="bn_eval", inputs=_X16, layers=[_rl("conv", "x", "y", 16, 16, k=3, bn="eval", act="lrelu")], outs=["y"],
          raises=(NotImplementedError, "backward through eval-mode BatchNorm is not supported"),
          calls=["rd_conv_pack_weights", "rd_conv_fwd", "rd_bn_finalize", "rd_affine_act"]),
