@@ -282,6 +282,17 @@ int rd_bn_act_bwd_recompute_phases(const void* dz, const void* z, const void* y,
 int rd_bn_act_bwd_from_partial(const void* dz, const void* y, const float* mean, const float* rstd, const float* scale, const float* shift,
                                const float* partial, int32_t rows, int32_t row_channels, float* coef, float* dgamma, float* dbeta, int32_t accumulate,
                                void* dy, int64_t pixels, int32_t C, int32_t act, float slope, int32_t dtype, void* stream);
+/* Backward through a BatchNorm that normalised with its RUNNING statistics (rd_bn_finalize with training = 0 wrote mean = running_mean,
+ * rstd = 1 / sqrt(running_var + eps), scale, shift): mean and rstd are constants, so g = dz * act'(.), dy = scale[c] * g, dres (optional;
+ * its presence says the layer had a residual) = g, dbeta[c] = sum g, dgamma[c] = sum g * (y - mean[c]) * rstd[c].  ONE pass over dz and y
+ * writes dy (three tensor passes; rd_bn_act_bwd_recompute makes five) and, when dgamma or dbeta is given, the rd_bn_bwd_rows rows of
+ * `partial`, which the family's finalize launch sums in double precision (accumulate: add to what the gradient buffers hold).  dgamma and dbeta
+ * both NULL: one launch, `partial` is not touched and may be NULL.  Without dres the activation's argument is recomputed from y as
+ * scale * y + shift (rd_affine_act's expression) for EVERY channel count, so z may be NULL; with dres the derivative is read from z, as
+ * rd_bn_act_bwd does, and a NULL z is refused. */
+int rd_bn_act_bwd_frozen(const void* dz, const void* z, const void* y, const float* mean, const float* rstd, const float* scale,
+                         const float* shift, float* partial, float* dgamma, float* dbeta, int32_t accumulate, void* dy, void* dres,
+                         int64_t pixels, int32_t C, int32_t act, float slope, int32_t dtype, void* stream);
 /* ---- Decoder head: the last decoder convolution's BatchNorm + activation fused with the one-channel 3x3 output convolution.
  * Replaces, for RCNet/networks.py:773-779 (MultiScaleDecoder.forward: deconv0 -> output0; output0 = net_utils.Conv2d(16 -> 1, 3x3, bias=False,
  * no BatchNorm, linear: utils/net_utils.py:50-91), the chain BatchNorm2d apply + LeakyReLU -> conv2d and its autograd backward (conv2d data +
@@ -306,7 +317,8 @@ int rd_bn_head_bwd_apply(const void* dlogits, const void* y, const float* mean, 
 /* instantiation name (as rd_conv_fwd_kernel_name) of which = 0: forward, 1: backward reduce, 2: backward apply */
 const char* rd_bn_head_kernel_name(int32_t which, int32_t dtype, int32_t act);
 /* instantiation name (as rd_conv_fwd_kernel_name) of which = 0: rd_affine_act (flag = residual given), 1: the BatchNorm-backward reduce
-   pass, 2: its apply pass (flag = recompute form) for this channel count / dtype / activation */
+   pass, 2: its apply pass (flag = recompute form), 3: rd_bn_act_bwd_frozen (flag bit 0 = sums wanted, bit 1 = dres given) for this
+   channel count / dtype / activation */
 const char* rd_bn_kernel_name(int32_t which, int32_t C, int32_t dtype, int32_t act, int32_t flag);
 int rd_act_bwd(const void* dz, const void* z, void* dx, int64_t n, int32_t act, float slope, int32_t dtype, void* stream);
 /* bias gradient: out[c] (+)= sum over rows of x[rows][C] */

@@ -503,6 +503,18 @@ int rd_bn_act_bwd_recompute(const void* dz, const void* z, const void* y, const 
   return rd_bn_act_bwd_recompute_phases(dz, z, y, mean, rstd, scale, shift, partial, coef, dgamma, dbeta, accumulate, dy, dres, pixels, C, act, slope,
                                         dtype, 7, stream);
 }
+int rd_bn_act_bwd_frozen(const void* dz, const void* z, const void* y, const float* mean, const float* rstd, const float* scale,
+                         const float* shift, float* partial, float* dgamma, float* dbeta, int32_t accumulate, void* dy, void* dres,
+                         int64_t pixels, int32_t C, int32_t act, float slope, int32_t dtype, void* stream) {
+  if (!dz || !y || !mean || !rstd || !scale || !shift || !dy || !dt_ok(dtype) || pixels < 0 || C <= 0) return fail("bn_act_bwd_frozen: bad args");
+  if (dres && !z) return fail("bn_act_bwd_frozen: a layer with a residual (dres given) takes the activation's derivative from z");
+  if ((dgamma || dbeta) && !partial) return fail("bn_act_bwd_frozen: parameter gradients need the partial rows (rd_bn_bwd_rows)");
+  if (pixels == 0) return 0;
+  if (!dgamma && !dbeta) partial = nullptr;      // nothing wants the sums: one launch, no rows
+  RD_NS(dtype, launch_bn_frozen_bwd)(dz, z, y, mean, rstd, scale, shift, partial, dy, dres, pixels, C, act, slope, RD_DT(dtype), S(stream));
+  if (partial) rd::launch_bn_bwd_finalize(partial, rd::bn_bwd_rows(pixels, C), C, (double)pixels, dgamma, dbeta, accumulate, nullptr, nullptr, S(stream));
+  return done("rd_bn_act_bwd_frozen");
+}
 /* ---- decoder head (rd_head.hip): BatchNorm + activation of the last decoder convolution fused with the one-channel 3x3 output convolution */
 int32_t rd_bn_head_ok(int32_t N, int32_t H, int32_t W, int32_t C, int32_t dtype) {
   return dt_ok(dtype) && RD_NS(dtype, bn_head_ok)(N, H, W, C, RD_DT(dtype)) ? 1 : 0;
@@ -539,7 +551,7 @@ const char* rd_bn_head_kernel_name(int32_t which, int32_t dtype, int32_t act) {
   return RD_NS(dtype, bn_head_kernel_name)(which, RD_DT(dtype), act);
 }
 const char* rd_bn_kernel_name(int32_t which, int32_t C, int32_t dtype, int32_t act, int32_t flag) {
-  if (!dt_ok(dtype) || which < 0 || which > 2 || C <= 0) return "";
+  if (!dt_ok(dtype) || which < 0 || which > 3 || C <= 0) return "";
   return RD_NS(dtype, bn_kernel_name)(which, C, RD_DT(dtype), act, flag);
 }
 int rd_act_bwd(const void* dz, const void* z, void* dx, int64_t n, int32_t act, float slope, int32_t dtype, void* stream) {

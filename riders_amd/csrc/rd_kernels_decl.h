@@ -91,6 +91,9 @@ void launch_bn_bwd_finalize(const float* partial, int rows, int C, double count,
 void launch_bn_bwd_apply(const void* dz, const void* z, const void* y, const float* mean, const float* rstd,
                          const float* scale, const float* c1, const float* c2, void* dy, void* dres, int64_t pixels,
                          int C, int act, float slope, int dtype, hipStream_t st, const float* shift = nullptr);
+void launch_bn_frozen_bwd(const void* dz, const void* z, const void* y, const float* mean, const float* rstd, const float* scale,
+                          const float* shift, float* partial, void* dy, void* dres, int64_t pixels, int C, int act, float slope, int dtype,
+                          hipStream_t st);
 void launch_act_bwd(const void* dz, const void* z, void* dx, int64_t n, int act, float slope, int dtype, hipStream_t st);
 void launch_colsum(const void* x, float* partial, float* out, int accumulate, int64_t rows, int C, int dtype, hipStream_t st);
 int colsum_rows(int64_t rows, int C);

@@ -770,13 +770,20 @@ void launch_affine_act_add(const void* y, const float* scale, const float* shift
 }
 
 // instantiation names as rocprofv3's kernel trace prints them (bench.py attributes HIP-event timings to kernels by these names):
-// which 0 = rd_affine_act (flag: residual present), 1 = BatchNorm-backward reduce, 2 = BatchNorm-backward apply (flag: recompute form)
+// which 0 = rd_affine_act (flag: residual present), 1 = BatchNorm-backward reduce, 2 = BatchNorm-backward apply (flag: recompute form),
+// 3 = the frozen (running-statistics) backward
 const char* bn_kernel_name(int which, int C, int dtype, int act, int flag) {
   static thread_local char buf[96];
   const char* T = dtype == 0 ? "float" : RD_T16_NAME;
   const bool v = vec_ok(C, dtype), g = !v && gen_ok(C, dtype);
   const char* form = v ? "vec" : "gen";
   const int A = (act >= 0 && act <= 3) ? act : -1;
+  if (which == 3) {      // the frozen backward: flag bit 0 = the sums are wanted, bit 1 = the derivative is read from z (dres given)
+    const char* S = (flag & 1) ? "true" : "false"; const char* Z = (flag & 2) ? "true" : "false";
+    if (v || g) snprintf(buf, sizeof(buf), "bn_frozen_bwd_%s_kernel<%s, %s, %s, %d>", form, T, S, Z, A);
+    else snprintf(buf, sizeof(buf), "bn_frozen_bwd_kernel<%s, %s, %s>", T, S, Z);
+    return buf;
+  }
   if (!(v || g)) flag = which == 0 ? flag : 0;
   if (which == 0) {
     if (v || g) snprintf(buf, sizeof(buf), "affine_act_%s_kernel<%s, %d, %s>", form, T, A, flag ? "true" : "false");
@@ -858,6 +865,249 @@ void launch_bn_bwd_apply(const void* dz, const void* z, const void* y, const flo
   if (dtype == 0) { if (v4) RD_BA(float, true); else RD_BA(float, false); }
   else { if (v4) RD_BA(bf16_t, true); else RD_BA(bf16_t, false); }
 #undef RD_BA
+}
+
+// ---- backward through a BatchNorm that normalises with its running statistics (frozen / eval mode).  mean and rstd are constants of the
+// layer, so dy = scale * g needs neither batch sum: ONE pass reads dz and y and writes dy (three tensor passes; the training-mode backward
+// makes five), and where gamma / beta want gradients the same pass leaves the (sum g, sum g * xhat) rows that bn_bwd_finalize_kernel sums.
+// g = dz * act'(u).  FROMZ (the layer had a residual, dres is written): u is read from z, as bn_bwd_apply_kernel does; otherwise u is
+// recomputed from y with rd_affine_act's own expression scale * y + shift, in all three channel-count forms -- z is never needed.
+// SUMS: block b owns the pixels [b * per, (b + 1) * per) (col_reduce's geometry and summation order); otherwise a plain grid-stride loop.
+template <typename T, bool SUMS, bool FROMZ, int ACT>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_vec_kernel(const T* __restrict__ dz, const T* __restrict__ z, const T* __restrict__ y,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                float* __restrict__ partial, T* __restrict__ dy, T* __restrict__ dres,
+                                                                int64_t pixels, int C, int act, float slope) {
+  constexpr int VE = Elem<T>::VE;
+  const int actv = ACT >= 0 ? ACT : act;
+  __shared__ float red[SUMS ? 256 * VE * 2 : 2];
+  const int t = threadIdx.x;
+  const int VP = C / VE;
+  int64_t i, vend, step;
+  if (SUMS) {
+    const int64_t per = cdiv(pixels, (int64_t)gridDim.x);
+    const int64_t pbeg = (int64_t)blockIdx.x * per, pend = pbeg + per < pixels ? pbeg + per : pixels;
+    i = pbeg * VP + t; vend = pend * VP; step = 256;
+  } else {
+    i = (int64_t)blockIdx.x * 256 + t; vend = pixels * VP; step = (int64_t)gridDim.x * 256;
+  }
+  const int c0 = (t % VP) * VE;      // 256 % VP == 0: a thread keeps its channel vector for the whole loop
+  float mu[VE], rs[VE], sc[VE], sh[VE], a[VE], b[VE];
+#pragma unroll
+  for (int e = 0; e < VE; e++) {
+    a[e] = 0.f; b[e] = 0.f;
+    mu[e] = SUMS ? mean[c0 + e] : 0.f; rs[e] = SUMS ? rstd[c0 + e] : 1.f;
+    sc[e] = scale[c0 + e]; sh[e] = FROMZ ? 0.f : shift[c0 + e];
+  }
+  auto one = [&](int64_t o, float (&gg)[VE], const float (&zz)[VE], const float (&yy)[VE]) RD_INLINE_LAMBDA {
+    float ov[VE];
+#pragma unroll
+    for (int e = 0; e < VE; e++) {
+      if (actv) gg[e] *= act_grad_from_out(FROMZ ? zz[e] : yy[e] * sc[e] + sh[e], actv, slope);
+      ov[e] = sc[e] * gg[e];
+      if (SUMS) { a[e] += gg[e]; b[e] += gg[e] * ((yy[e] - mu[e]) * rs[e]); }
+    }
+    stv(dy + o, ov);
+    if (FROMZ) stv(dres + o, gg);
+  };
+  for (; i + step < vend; i += 2 * step) {      // two vectors per iteration, every request issued before the first use
+    float g0[VE], z0[VE], y0[VE], g1[VE], z1[VE], y1[VE];
+    ldv(dz + i * VE, g0); ldv(dz + (i + step) * VE, g1);
+    if (FROMZ && actv) { ldv(z + i * VE, z0); ldv(z + (i + step) * VE, z1); }
+    ldv(y + i * VE, y0); ldv(y + (i + step) * VE, y1);
+    one(i * VE, g0, z0, y0); one((i + step) * VE, g1, z1, y1);
+  }
+  for (; i < vend; i += step) {
+    float g0[VE], z0[VE], y0[VE];
+    ldv(dz + i * VE, g0);
+    if (FROMZ && actv) ldv(z + i * VE, z0);
+    ldv(y + i * VE, y0);
+    one(i * VE, g0, z0, y0);
+  }
+  if (SUMS) {      // col_reduce_vec_kernel's combine: lanes of a wave that share a channel group, fixed xor tree, then the waves in order
+    for (int o = 32; o >= VP; o >>= 1) {
+#pragma unroll
+      for (int e = 0; e < VE; e++) { a[e] += __shfl_xor(a[e], o); b[e] += __shfl_xor(b[e], o); }
+    }
+#pragma unroll
+    for (int e = 0; e < VE; e++) { red[(t * VE + e) * 2] = a[e]; red[(t * VE + e) * 2 + 1] = b[e]; }
+    __syncthreads();
+    for (int c = t; c < C; c += 256) {
+      const int g = c / VE, e = c - g * VE;
+      float sa = 0.f, sb = 0.f;
+      for (int tt = g; tt < 256; tt += VP)
+        if ((tt & 63) < VP) { sa += red[(tt * VE + e) * 2]; sb += red[(tt * VE + e) * 2 + 1]; }
+      partial[((int64_t)blockIdx.x * C + c) * 2] = sa;
+      partial[((int64_t)blockIdx.x * C + c) * 2 + 1] = sb;
+    }
+  }
+}
+
+// any channel count with whole vectors, at most 256 of them: thread t owns channel group t % VP of pixel slot t / VP (affine_act_gen_kernel)
+template <typename T, bool SUMS, bool FROMZ, int ACT>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_gen_kernel(const T* __restrict__ dz, const T* __restrict__ z, const T* __restrict__ y,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                float* __restrict__ partial, T* __restrict__ dy, T* __restrict__ dres,
+                                                                int64_t pixels, int C, int act, float slope) {
+  constexpr int VE = Elem<T>::VE;
+  const int actv = ACT >= 0 ? ACT : act;
+  __shared__ float red[SUMS ? 256 * VE * 2 : 2];
+  const int t = threadIdx.x;
+  const int VP = C / VE, PPB = 256 / VP;
+  const int g = t % VP, pl = t / VP;
+  int64_t p, pend, step;
+  if (SUMS) {
+    const int64_t per = cdiv(pixels, (int64_t)gridDim.x);
+    const int64_t pbeg = (int64_t)blockIdx.x * per;
+    pend = pbeg + per < pixels ? pbeg + per : pixels;
+    p = pbeg + pl; step = PPB;
+  } else {
+    p = (int64_t)blockIdx.x * PPB + pl; pend = pixels; step = (int64_t)gridDim.x * PPB;
+  }
+  float mu[VE], rs[VE], sc[VE], sh[VE], a[VE], b[VE];
+#pragma unroll
+  for (int e = 0; e < VE; e++) {
+    const int c = g * VE + e;
+    a[e] = 0.f; b[e] = 0.f;
+    mu[e] = SUMS ? mean[c] : 0.f; rs[e] = SUMS ? rstd[c] : 1.f;
+    sc[e] = scale[c]; sh[e] = FROMZ ? 0.f : shift[c];
+  }
+  auto one = [&](int64_t o, float (&gg)[VE], const float (&zz)[VE], const float (&yy)[VE]) RD_INLINE_LAMBDA {
+    float ov[VE];
+#pragma unroll
+    for (int e = 0; e < VE; e++) {
+      if (actv) gg[e] *= act_grad_from_out(FROMZ ? zz[e] : yy[e] * sc[e] + sh[e], actv, slope);
+      ov[e] = sc[e] * gg[e];
+      if (SUMS) { a[e] += gg[e]; b[e] += gg[e] * ((yy[e] - mu[e]) * rs[e]); }
+    }
+    stv(dy + o, ov);
+    if (FROMZ) stv(dres + o, gg);
+  };
+  if (pl < PPB) {
+    for (; p + step < pend; p += 2 * step) {      // two pixels per iteration (small maps are latency-bound otherwise)
+      const int64_t o0 = p * C + g * VE, o1 = (p + step) * C + g * VE;
+      float g0[VE], z0[VE], y0[VE], g1[VE], z1[VE], y1[VE];
+      ldv(dz + o0, g0); ldv(dz + o1, g1);
+      if (FROMZ && actv) { ldv(z + o0, z0); ldv(z + o1, z1); }
+      ldv(y + o0, y0); ldv(y + o1, y1);
+      one(o0, g0, z0, y0); one(o1, g1, z1, y1);
+    }
+    for (; p < pend; p += step) {
+      const int64_t o0 = p * C + g * VE;
+      float g0[VE], z0[VE], y0[VE];
+      ldv(dz + o0, g0);
+      if (FROMZ && actv) ldv(z + o0, z0);
+      ldv(y + o0, y0);
+      one(o0, g0, z0, y0);
+    }
+  }
+  if (SUMS) {      // col_reduce_gen_kernel's combine: the pixel slots of a channel in slot order
+#pragma unroll
+    for (int e = 0; e < VE; e++) { red[(t * VE + e) * 2] = a[e]; red[(t * VE + e) * 2 + 1] = b[e]; }
+    __syncthreads();
+    for (int c = t; c < C; c += 256) {
+      const int gg = c / VE, e = c - gg * VE;
+      float sa = 0.f, sb = 0.f;
+      for (int q = 0; q < PPB; q++) { sa += red[((q * VP + gg) * VE + e) * 2]; sb += red[((q * VP + gg) * VE + e) * 2 + 1]; }
+      partial[((int64_t)blockIdx.x * C + c) * 2] = sa;
+      partial[((int64_t)blockIdx.x * C + c) * 2 + 1] = sb;
+    }
+  }
+}
+
+// every other channel count: col_reduce_kernel's geometry (thread = pixel lane x channel, grid = pixel ranges x channel chunks), with and
+// without the sums; four pixels' loads in flight per iteration, accumulated in pixel order
+template <typename T, bool SUMS, bool FROMZ>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const T* __restrict__ dz, const T* __restrict__ z, const T* __restrict__ y,
+                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            float* __restrict__ partial, T* __restrict__ dy, T* __restrict__ dres,
+                                                            int64_t pixels, int C, int CB, int PL, int act, float slope) {
+  __shared__ float red[SUMS ? 2 : 1][SUMS ? 256 : 1];
+  const int t = threadIdx.x;
+  const int cl = t % CB, pl = t / CB;
+  const int c = blockIdx.y * CB + cl;
+  const int64_t per = cdiv(pixels, (int64_t)gridDim.x);
+  const int64_t pbeg = (int64_t)blockIdx.x * per, pend = pbeg + per < pixels ? pbeg + per : pixels;
+  float a = 0.f, b = 0.f;
+  if (c < C) {
+    const float mu = SUMS ? mean[c] : 0.f, rs = SUMS ? rstd[c] : 1.f, sc = scale[c], sh = FROMZ ? 0.f : shift[c];
+    int64_t p = pbeg + pl;
+    for (; p + 3 * (int64_t)PL < pend; p += 4 * (int64_t)PL) {
+      float g[4], zz[4] = {0.f, 0.f, 0.f, 0.f}, yy[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int64_t i = (p + q * (int64_t)PL) * C + c;
+        g[q] = Elem<T>::ld(dz + i);
+        if (FROMZ && act) zz[q] = Elem<T>::ld(z + i);
+        yy[q] = Elem<T>::ld(y + i);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int64_t i = (p + q * (int64_t)PL) * C + c;
+        float gq = g[q];
+        if (act) gq *= act_grad_from_out(FROMZ ? zz[q] : yy[q] * sc + sh, act, slope);
+        Elem<T>::st(dy + i, sc * gq);
+        if (FROMZ) Elem<T>::st(dres + i, gq);
+        if (SUMS) { a += gq; b += gq * ((yy[q] - mu) * rs); }
+      }
+    }
+    for (; p < pend; p += PL) {
+      const int64_t i = p * C + c;
+      float gq = Elem<T>::ld(dz + i);
+      const float yv = Elem<T>::ld(y + i);
+      if (act) gq *= act_grad_from_out(FROMZ ? Elem<T>::ld(z + i) : yv * sc + sh, act, slope);
+      Elem<T>::st(dy + i, sc * gq);
+      if (FROMZ) Elem<T>::st(dres + i, gq);
+      if (SUMS) { a += gq; b += gq * ((yv - mu) * rs); }
+    }
+  }
+  if (SUMS) {
+    red[0][t] = a; red[1][t] = b;
+    __syncthreads();
+    if (pl == 0 && c < C) {
+      float sa = 0.f, sb = 0.f;
+      for (int q = 0; q < PL; q++) { sa += red[0][q * CB + cl]; sb += red[1][q * CB + cl]; }
+      partial[((int64_t)blockIdx.x * C + c) * 2] = sa;
+      partial[((int64_t)blockIdx.x * C + c) * 2 + 1] = sb;
+    }
+  }
+}
+
+// partial != nullptr: the pass also writes bn_bwd_rows(pixels, C) rows of (sum g, sum g * xhat); dres != nullptr: the derivative is read from z
+void launch_bn_frozen_bwd(const void* dz, const void* z, const void* y, const float* mean, const float* rstd, const float* scale,
+                          const float* shift, float* partial, void* dy, void* dres, int64_t pixels, int C, int act, float slope, int dtype,
+                          hipStream_t st) {
+  const bool sums = partial != nullptr, fromz = dres != nullptr;
+  const int ve = dtype == 0 ? 4 : 8;
+  const int rows = red_rows(pixels, C);
+#define RD_FZ(K, T, S, Z, GRID, ...) hipLaunchKernelGGL((K<T, S, Z, ##__VA_ARGS__>), GRID, dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, shift, partial, (T*)dy, (T*)dres, pixels, C, RD_FZ_TAIL)
+#define RD_FZ4(K, T, GRID, ...) do { if (sums) { if (fromz) RD_FZ(K, T, true, true, GRID, ##__VA_ARGS__); else RD_FZ(K, T, true, false, GRID, ##__VA_ARGS__); } \
+                                     else { if (fromz) RD_FZ(K, T, false, true, GRID, ##__VA_ARGS__); else RD_FZ(K, T, false, false, GRID, ##__VA_ARGS__); } } while (0)
+  if (vec_ok(C, dtype) || gen_ok(C, dtype)) {
+    const bool v = vec_ok(C, dtype);
+    const int ppb = 256 / (C / ve);
+    // no sums: two vectors / two pixels per thread and iteration, as the training-mode apply kernels' grids
+    const unsigned gx = sums ? (unsigned)rows : v ? ew_grid_per(pixels * (C / ve), 2) : (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(pixels, 2 * ppb), 2048));
+    const dim3 grid(gx);
+#define RD_FZ_TAIL act, slope
+    act_dispatch(act, [&](auto ac) {
+      constexpr int A = decltype(ac)::value;
+      if (v) { if (dtype == 0) RD_FZ4(bn_frozen_bwd_vec_kernel, float, grid, A); else RD_FZ4(bn_frozen_bwd_vec_kernel, bf16_t, grid, A); }
+      else { if (dtype == 0) RD_FZ4(bn_frozen_bwd_gen_kernel, float, grid, A); else RD_FZ4(bn_frozen_bwd_gen_kernel, bf16_t, grid, A); }
+    });
+#undef RD_FZ_TAIL
+    return;
+  }
+  RedGeom g = red_geom(C);
+  const dim3 grid(rows, g.nchunk);
+#define RD_FZ_TAIL g.CB, g.PL, act, slope
+  if (dtype == 0) RD_FZ4(bn_frozen_bwd_kernel, float, grid); else RD_FZ4(bn_frozen_bwd_kernel, bf16_t, grid);
+#undef RD_FZ_TAIL
+#undef RD_FZ4
+#undef RD_FZ
 }
 
 void launch_act_bwd(const void* dz, const void* z, void* dx, int64_t n, int act, float slope, int dtype, hipStream_t st) {

@@ -102,7 +102,8 @@ def apply_opts(spec):
 
 
 # how often a virtual activation was consumed in place / had to be written after all (tests assert that the fused routes are taken)
-lazy_counts = {"fwd_fused": 0, "wgrad_fused": 0, "add_fused": 0, "materialized": 0, "bn_bwd_fused": 0, "head_fused": 0, "head_unfused_bwd": 0, "up2_fwd": 0, "up2_dgrad": 0}
+lazy_counts = {"fwd_fused": 0, "wgrad_fused": 0, "add_fused": 0, "materialized": 0, "bn_bwd_fused": 0, "head_fused": 0, "head_unfused_bwd": 0, "up2_fwd": 0, "up2_dgrad": 0,
+               "bn_frozen": 0, "bn_frozen_sums": 0}      # launches of the frozen BatchNorm backward without / with the parameter-gradient sums
 
 
 def head_route(C):
@@ -403,6 +404,114 @@ def _bn_backward(t, dz, z, y, coef, bn, act, slope, has_res, need_res, part=None
                                     _p(dbet), acc, _p(dy), _p(dres), pixels, C, act, slope, dt, st)
     _chk(_tb("bn_backward", (4 + (dres is not None)) * b_out, bwd, "bn backward(res) M=%d C=%d" % (pixels, C)) if timed else bwd(), "rd_bn_act_bwd")
     return dy, dres
+
+
+def bn_trains(bn, training=None):
+    """The one rule for a BatchNorm layer's mode, taken from the module itself: True = batch statistics (and the running statistics move),
+    False = the running statistics are used and left alone.  `training` is the module's own flag (bn.training when None); the sticky
+    _rd_frozen mark (riders_amd.freeze_batch_norm) overrides it; a layer without running statistics has nothing else to normalise with."""
+    if bn is None:
+        return False
+    tr = bn.training if training is None else bool(training)
+    return bool((tr and not getattr(bn, "_rd_frozen", False)) or not bn.track_running_stats)
+
+
+_bn_lists = weakref.WeakKeyDictionary()      # root module -> its BatchNorm2d modules (bn_signature)
+
+
+def bn_signature(*roots):
+    """graph-key part that names the BatchNorm modes below `roots` (modules, or objects holding some): per layer its bn_trains value and
+    whether gamma / beta want gradients -- a freeze, a thaw or a bn.eval() changes the launch sequence, so it must change the key"""
+    sig = []
+    for r in roots:      # (the module walk is cached per root: this runs in front of every forward of a captured region)
+        bns = _bn_lists.get(r) if isinstance(r, torch.nn.Module) else None
+        if bns is None:
+            bns = _bn_modules(r)
+            if isinstance(r, torch.nn.Module):
+                _bn_lists[r] = bns
+        sig += [_bn_sig1(m) for m in bns]
+    return tuple(sig)
+
+
+def _bn_sig1(m):
+    return (bn_trains(m), bool(m.weight is not None and m.weight.requires_grad), bool(m.bias is not None and m.bias.requires_grad))
+
+
+def _bn_modules(target):
+    """every torch.nn.BatchNorm2d below an nn.Module, an object with encoder / decoder (RCNetModel), or an iterable of either"""
+    if isinstance(target, torch.nn.Module):
+        return [m for m in target.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    if hasattr(target, "encoder") and hasattr(target, "decoder"):
+        return _bn_modules(target.encoder) + _bn_modules(target.decoder)
+    out = []
+    for x in target:
+        out += _bn_modules(x)
+    return out
+
+
+def _bn_forced_eval(forced):
+    """A layer's mode is its BatchNorm module's own (bn_trains(bn): bn.eval(), freeze_batch_norm) -- that is what the frozen backward serves, and
+    what every module of this package passes.  A direct engine call that passes training=False for a module which is itself live and not frozen
+    asks for the running statistics against the module's own word: the forward honours the flag, as it always did, and the backward stays
+    refused, as it always was -- freeze the module instead."""
+    if forced:
+        raise NotImplementedError("backward through eval-mode BatchNorm is not supported")
+
+
+def freeze_batch_norm(target, freeze=True, affine=True):
+    """Freeze (or thaw) every BatchNorm2d below `target` -- an nn.Module, an RCNetModel, or an iterable of modules: a frozen layer normalises
+    with its running statistics, leaves them and num_batches_tracked alone, and back-propagates through them (rd_bn_act_bwd_frozen).  The mark
+    (_rd_frozen) is sticky: a later model.train() does not thaw the layers -- the training loops call .train() after building or restoring a
+    model.  affine=False also stops gamma and beta from training (requires_grad cleared; thawing restores what they had).  state_dict keys
+    and values are untouched.  -> the number of layers marked."""
+    bns = _bn_modules(target)
+    for m in bns:
+        if freeze and not m.track_running_stats:
+            raise ValueError("freeze_batch_norm: a BatchNorm2d without running statistics (track_running_stats=False) has nothing to freeze to")
+    for m in bns:
+        if freeze:
+            m._rd_frozen = True
+            if not affine and m.weight is not None and not hasattr(m, "_rd_affine_req"):
+                m._rd_affine_req = (m.weight.requires_grad, m.bias.requires_grad)
+                m.weight.requires_grad_(False); m.bias.requires_grad_(False)
+        else:
+            m._rd_frozen = False
+        if (not freeze or affine) and hasattr(m, "_rd_affine_req"):
+            m.weight.requires_grad_(m._rd_affine_req[0]); m.bias.requires_grad_(m._rd_affine_req[1])
+            del m._rd_affine_req
+    return len(bns)
+
+
+def _bn_backward_frozen(t, dz, z, y, coef, bn, act, slope, has_res, need_res, timed=True):
+    """backward of _bn_forward with bn_train False (running statistics): dy = scale * g in ONE pass over (dz, y) -- rd_bn_act_bwd_frozen.
+    A HeadGrad is written out first (the fused head's backward kernels implement the training formula); gamma / beta that want no gradient
+    (or affine=False) take the launch without sums and get no gradient buffer; the activation's argument is recomputed from y for every
+    channel count, so a virtual output (z None) is fine; with a residual the derivative is read from z and dres is written."""
+    lib, dt, st = L(), rd_of(y), _stream(y)
+    C = y.shape[-1]
+    pixels, b_out = y.numel() // C, y.numel() * y.element_size()
+    if isinstance(dz, HeadGrad):
+        dz = dz.materialize(t)
+    dgam = dbet = partial = None
+    acc = 0
+    if bn.weight is not None and bn.weight.requires_grad:
+        dgam, acc = t.param_grad(bn.weight)
+    if bn.bias is not None and bn.bias.requires_grad:
+        dbet, acc2 = t.param_grad(bn.bias)
+        assert dgam is None or acc == acc2
+        acc = acc2
+    sums = dgam is not None or dbet is not None
+    if sums:
+        partial = torch.empty((lib.rd_bn_bwd_rows(pixels, C), C, 2), dtype=torch.float32, device=y.device)
+    lazy_counts["bn_frozen_sums" if sums else "bn_frozen"] += 1
+    dy = torch.empty_like(y)
+    dres = torch.empty_like(y) if has_res else None
+    bwd = lambda: lib.rd_bn_act_bwd_frozen(_p(dz), _p(z if has_res else None), _p(y), _p(coef[2]), _p(coef[3]), _p(coef[0]), _p(coef[1]),      # noqa: E731
+                                           _p(partial), _p(dgam), _p(dbet), acc, _p(dy), _p(dres), pixels, C, act, slope, dt, st)
+    flag = (1 if sums else 0) | (2 if has_res else 0)
+    _chk(_tb("bn_backward", (3 + 2 * has_res) * b_out, bwd, "bn backward(frozen%s) M=%d C=%d" % (", sums" if sums else "", pixels, C),
+             kernel=lambda: lib.rd_bn_kernel_name(3, C, dt, act, flag).decode()) if timed else bwd(), "rd_bn_act_bwd_frozen")
+    return dy, (dres if need_res else None)
 
 
 # ------------------------------------------------------------------------------------------------- tape
@@ -1340,7 +1449,8 @@ def _conv_plan(lib, x, x2, weight, bias, stride, pad, up, bn, act, slope, residu
     if out_hw is not None:  # asymmetric (TF-"SAME") padding: `pad` is the leading pad, the output size is given
         p.OH, p.OW = int(out_hw[0]), int(out_hw[1])
     p.use_bn = bn is not None
-    p.bn_train = p.use_bn and (training or not bn.track_running_stats)
+    p.bn_train = p.use_bn and bn_trains(bn, training)
+    p.bn_forced_eval = p.use_bn and not p.bn_train and bn_trains(bn)      # the caller's flag overrides a module that is itself live (_bn_forced_eval)
     p.conv_act = ACT_NONE if (p.use_bn or residual is not None) else act
     # exact-2x nearest up-sampling of one source (UpConv2d at 15x6 -> 30x12 ... 120x50 -> 240x100), and its 3x3 / stride 1 / pad 1 form
     p.exact2x = p.is_up and p.C2 == 0 and (p.Hin, p.Win) == (2 * p.H1, 2 * p.W1)
@@ -1353,7 +1463,7 @@ def _conv_plan(lib, x, x2, weight, bias, stride, pad, up, bn, act, slope, residu
         # (layers the streaming few-channel kernels take -- SML's 3 -> 3 `first` convolution -- are handed over as they are; an input that
         # needs a gradient -- the SML backbone's stem behind `first` -- gets it from the un-padded descriptor in _conv_bwd_data)
         p.C1 = p.cin_pad = (p.C1 + p.ve - 1) // p.ve * p.ve
-    p.lazy = bool(lazy_out and p.use_bn and residual is None and _state["lazy_bn"] >= int(lazy_out) and _state["bn_recompute"] and _bn_recomputes(p.Cout, p.dt))
+    p.lazy = bool(lazy_out and p.use_bn and residual is None and _state["lazy_bn"] >= int(lazy_out) and _state["bn_recompute"] and (not p.bn_train or _bn_recomputes(p.Cout, p.dt)))
     p.pixels = p.N * p.OH * p.OW
     p.flops = 2.0 * p.pixels * p.Cout * p.KH * p.KW * p.Cin  # algorithmic (2 FLOP per MAC), same count for dgrad / wgrad
     p.shp = "M=%d Cin=%d Cout=%d k=%d s=%d%s" % (p.pixels, p.Cin, p.Cout, p.KH, stride, " up" if p.is_up else "")
@@ -1440,8 +1550,9 @@ def _conv_epilogue(lib, p, y, stats, bn, residual):
 def _conv_bwd_act(t, p, s, dz, src):
     """backward of what _conv_epilogue ran: dz -> (dy, the residual's gradient)"""
     if p.use_bn:
-        if not p.bn_train:
-            raise NotImplementedError("backward through eval-mode BatchNorm is not supported")
+        if not p.bn_train:      # running statistics: no batch sums in dy, and no entry in t.bn_src (the sums of the data-gradient epilogue go with the training-mode apply)
+            _bn_forced_eval(p.bn_forced_eval)
+            return _bn_backward_frozen(t, dz, s.z, s.y, s.coef, s.bn, p.act, p.slope, s.residual is not None, p.need_res)
         return _bn_backward(t, dz, s.z, s.y, s.coef, s.bn, p.act, p.slope, s.residual is not None, p.need_res, src["partial"] if src is not None else None)
     if isinstance(dz, HeadGrad):
         dz = dz.materialize(t)
@@ -1652,7 +1763,7 @@ def conv_block(x, weight, *, x2=None, bias=None, stride=1, pad=None, up=None, bn
     if t is None:
         return zk
     p.need_in, p.need_res, p.w_req = t.requires(xk, x2), t.requires(residual), weight.requires_grad
-    if not (p.need_in or p.need_res or p.w_req or (p.use_bn and bn.weight is not None and bn.weight.requires_grad)):
+    if not (p.need_in or p.need_res or p.w_req or (p.use_bn and bn.weight is not None and (bn.weight.requires_grad or bn.bias.requires_grad))):
         return zk
     t.mark(zk)
     if p.bn_train and residual is None and _state["bn_recompute"] and _state["bn_bwd_fused"] and _bn_recomputes(p.Cout, p.dt):
@@ -2354,13 +2465,14 @@ def dwconv_block(x, weight, *, stride=1, pad=0, out_hw=None, bn=None, act=ACT_NO
     OH, OW = (int(out_hw[0]), int(out_hw[1])) if out_hw is not None else ((H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1)
     y = torch.empty((N, OH, OW, C), dtype=x.dtype, device=x.device)
     stats = None
-    srows = lib.rd_dwconv_stats_rows(N, OH, OW, C, k, stride) if (_state["dw_fused_stats"] and bn is not None and (training or not bn.track_running_stats)) else 0
+    srows = lib.rd_dwconv_stats_rows(N, OH, OW, C, k, stride) if (_state["dw_fused_stats"] and bn_trains(bn, training)) else 0
     if srows > 0:      # the BatchNorm statistics come out of the convolution's epilogue: no separate pass over y
         stats = torch.empty((srows, C, 2), dtype=torch.float32, device=x.device)
         _chk(lib.rd_dwconv_fwd_stats(_p(x), _p(weight.detach()), _p(y), _p(stats), N, H, W, C, OH, OW, k, stride, pad, dt, st), "rd_dwconv_fwd_stats")
     else:
         _chk(lib.rd_dwconv_fwd(_p(x), _p(weight.detach()), _p(y), N, H, W, C, OH, OW, k, stride, pad, dt, st), "rd_dwconv_fwd")
-    bn_train = bn is not None and (training or not bn.track_running_stats)
+    bn_train = bn_trains(bn, training)
+    forced_eval = bn is not None and not bn_train and bn_trains(bn)
     if bn is not None:
         if bn_train and stats is None:      # (a shape whose convolution kernel has no statistics epilogue, or dw_fused_stats off)
             stats = torch.empty((lib.rd_dw_rows(N * OH * OW, C), C, 2), dtype=torch.float32, device=x.device)
@@ -2379,8 +2491,8 @@ def dwconv_block(x, weight, *, stride=1, pad=0, out_hw=None, bn=None, act=ACT_NO
             return
         if bn is not None:
             if not bn_train:
-                raise NotImplementedError("backward through eval-mode BatchNorm is not supported")
-            dy, _ = _bn_backward(t, dz, z, y, coef, bn, act, slope, False, False, timed=False)
+                _bn_forced_eval(forced_eval)
+            dy, _ = (_bn_backward if bn_train else _bn_backward_frozen)(t, dz, z, y, coef, bn, act, slope, False, False, timed=False)
         else:
             dy = dz
         if weight.requires_grad:

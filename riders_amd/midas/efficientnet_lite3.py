@@ -40,14 +40,25 @@ class _Counted(nn.Module):
     """BN layers bump num_batches_tracked lazily on the host (flushed when a state_dict is taken)."""
 
     def _setup_counter(self, bns):
-        self._bns, self._pending = bns, 0
+        self._bns, self._pending = bns, [0] * len(bns)
         self.register_state_dict_pre_hook(lambda m, p, k: m._flush())
 
+    def _count(self, delta=1):
+        """one forward (or `delta` replays of one): each BatchNorm that runs in training mode (engine.bn_trains: its own flag, not
+        frozen) counts a batch -- per layer, not per block"""
+        for i, b in enumerate(self._bns):
+            if bn_counts(getattr(self, b)):
+                self._pending[i] += delta
+
     def _flush(self):
-        if self._pending:
-            for b in self._bns:
-                getattr(self, b).num_batches_tracked += self._pending
-            self._pending = 0
+        for i, b in enumerate(self._bns):
+            if self._pending[i]:
+                getattr(self, b).num_batches_tracked += self._pending[i]
+                self._pending[i] = 0
+
+
+def bn_counts(bn):
+    return bn.num_batches_tracked is not None and engine.bn_trains(bn)
 
 
 def _conv_same(x, conv, bn, act, training, residual=None):
@@ -78,10 +89,9 @@ class DepthwiseSeparableConv(_Counted):
         self._setup_counter(["bn1", "bn2"])
 
     def _fwd(self, x):
-        if self.training:
-            self._pending += 1
-        h = _dw_same(x, self.conv_dw, self.bn1, ACT_RELU6, self.training)
-        return _conv_same(h, self.conv_pw, self.bn2, ACT_NONE, self.training, residual=x if self.has_residual else None)
+        self._count()
+        h = _dw_same(x, self.conv_dw, self.bn1, ACT_RELU6, self.bn1.training)
+        return _conv_same(h, self.conv_pw, self.bn2, ACT_NONE, self.bn2.training, residual=x if self.has_residual else None)
 
 
 class InvertedResidual(_Counted):
@@ -100,11 +110,10 @@ class InvertedResidual(_Counted):
         self._setup_counter(["bn1", "bn2", "bn3"])
 
     def _fwd(self, x):
-        if self.training:
-            self._pending += 1
-        h = _conv_same(x, self.conv_pw, self.bn1, ACT_RELU6, self.training)
-        h = _dw_same(h, self.conv_dw, self.bn2, ACT_RELU6, self.training)
-        return _conv_same(h, self.conv_pwl, self.bn3, ACT_NONE, self.training, residual=x if self.has_residual else None)
+        self._count()
+        h = _conv_same(x, self.conv_pw, self.bn1, ACT_RELU6, self.bn1.training)
+        h = _dw_same(h, self.conv_dw, self.bn2, ACT_RELU6, self.bn2.training)
+        return _conv_same(h, self.conv_pwl, self.bn3, ACT_NONE, self.bn3.training, residual=x if self.has_residual else None)
 
 
 class _Stem(_Counted):
@@ -147,11 +156,11 @@ def make_pretrained():
     return pre
 
 
-def run_layer1(layer1, x, training):
+def run_layer1(layer1, x):
     conv, bn = layer1[0], layer1[1]
-    if training:
+    if bn_counts(bn):
         layer1._stem_pending = getattr(layer1, "_stem_pending", 0) + 1
-    h = _conv_same(x, conv, bn, ACT_RELU6, training)
+    h = _conv_same(x, conv, bn, ACT_RELU6, bn.training)
     for stage in (layer1[3], layer1[4]):
         for blk in stage:
             h = blk._fwd(h)

@@ -66,12 +66,11 @@ class MidasNet_small_videpth(BaseModel):
 
     def _fwd(self, x, d):
         """x (B,H,W,C) activation dtype, d (B,H,W,1) fp32 -> pred (B,H,W,1) fp32."""
-        tr = self.training
-        if tr:
-            self._first_pending += 1
         c, bn = self.first[0], self.first[1]
-        layer_0 = engine.conv_block(x, c.weight, bias=c.bias, bn=bn, act=ACT_RELU, training=tr)
-        layer_1 = efficientnet_lite3.run_layer1(self.pretrained.layer1, layer_0, tr)
+        if efficientnet_lite3.bn_counts(bn):
+            self._first_pending += 1
+        layer_0 = engine.conv_block(x, c.weight, bias=c.bias, bn=bn, act=ACT_RELU, training=bn.training)      # (the BatchNorm's own mode)
+        layer_1 = efficientnet_lite3.run_layer1(self.pretrained.layer1, layer_0)
         layer_2 = efficientnet_lite3.run_stages(self.pretrained.layer2, layer_1)
         layer_3 = efficientnet_lite3.run_stages(self.pretrained.layer3, layer_2)
         engine.stage_mark("layer4_done")      # backward-order boundaries for the bucketed gradient all-reduce (parallel.sml_stages)
@@ -96,18 +95,20 @@ class MidasNet_small_videpth(BaseModel):
             pred = self._fwd(engine.from_nchw(x), dd)
             return engine.alias(pred, pred.view(dd.shape))
         # (d is a region INPUT: a captured region -- engine.set_autograph -- reads it from a static tensor)
-        return engine.run_region(run, (x, dd), list(self.parameters()), graph_key=("MidasNet_small_videpth.forward", id(self), self.training),
+        return engine.run_region(run, (x, dd), list(self.parameters()), graph_key=("MidasNet_small_videpth.forward", id(self), self.training, engine.bn_signature(self)),
                                  on_replay=self._bn_replay)
 
-    def _bn_replay(self):
-        """host-side bookkeeping of one replayed forward: the num_batches_tracked counters this module's _fwd bumps"""
-        from .efficientnet_lite3 import _Counted
-        if self.training:
-            for m in self.modules():
-                if isinstance(m, _Counted):
-                    m._pending += 1
-            self._first_pending += 1
-            self.pretrained.layer1._stem_pending = getattr(self.pretrained.layer1, "_stem_pending", 0) + 1
+    def _bn_replay(self, delta=1):
+        """host-side bookkeeping of `delta` replayed forwards: the num_batches_tracked counters this module's _fwd bumps, per BatchNorm
+        layer that runs in training mode"""
+        from .efficientnet_lite3 import _Counted, bn_counts
+        for m in self.modules():
+            if isinstance(m, _Counted):
+                m._count(delta)
+        if bn_counts(self.first[1]):
+            self._first_pending += delta
+        if bn_counts(self.pretrained.layer1[1]):
+            self.pretrained.layer1._stem_pending = getattr(self.pretrained.layer1, "_stem_pending", 0) + delta
 
 
 class MidasNet_small_depth(BaseModel):

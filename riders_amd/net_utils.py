@@ -56,6 +56,11 @@ class _BNCounter:
         self._nbt_pending = 0
         self.register_state_dict_pre_hook(lambda m, prefix, keep_vars: m._bn_flush())
 
+    def _bn_counts(self):
+        """this module's BatchNorm runs in training mode (engine.bn_trains: its own flag, not frozen) and has a counter to bump"""
+        bn = self.batch_norm if getattr(self, 'use_batch_norm', False) else None
+        return bn is not None and bn.num_batches_tracked is not None and engine.bn_trains(bn)
+
     def _bn_flush(self):
         if getattr(self, '_nbt_pending', 0) and getattr(self, 'use_batch_norm', False):
             self.batch_norm.num_batches_tracked += self._nbt_pending
@@ -83,10 +88,11 @@ class Conv2d(torch.nn.Module, _BNCounter):
         stays virtual (engine.LazyAct) and the consumer applies scale / shift / activation while it stages the raw convolution output."""
         act, slope = _act_code(self.activation_func)
         bn = self.batch_norm if self.use_batch_norm else None
-        if bn is not None and self.training:
+        if self._bn_counts():
             self._nbt_pending += 1
+        # the BatchNorm's OWN mode (bn.eval() under a parent in .train(), riders_amd.freeze_batch_norm), not the parent's flag
         return engine.conv_block(x, self.conv.weight, x2=x2, stride=self.conv.stride[0], pad=self.conv.padding[0], up=up,
-                                 bn=bn, act=act, slope=slope, training=self.training, lazy_out=lazy)
+                                 bn=bn, act=act, slope=slope, training=bn is not None and bn.training, lazy_out=lazy)
 
     def forward(self, x):
         def run(x):

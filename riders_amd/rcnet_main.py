@@ -325,7 +325,7 @@ class GraphedTrainStep(GraphedStep):
 
         def bump(delta):
             for m in bn:
-                if m.training:
+                if m._bn_counts():      # per BatchNorm: only layers that run in training mode count a batch
                     m._nbt_pending += delta
         buffers = [b for net in nets for b in net.buffers() if b.is_floating_point()]
         self.static_batch = tuple(batch)

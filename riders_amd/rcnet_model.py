@@ -58,7 +58,7 @@ class RCNetModel(object):
             return engine.to_nchw_out(logits, torch.float32)
         params = list(enc.parameters()) + list(dec.parameters())
         # (the RoI rows are a region INPUT: a captured region -- engine.set_autograph -- reads them from a static tensor)
-        logits = engine.run_region(run, (image, point, rois), params, graph_key=("RCNetModel.forward", id(enc), id(dec), enc.training, dec.training, tuple(shape)),
+        logits = engine.run_region(run, (image, point, rois), params, graph_key=("RCNetModel.forward", id(enc), id(dec), enc.training, dec.training, engine.bn_signature(enc, dec), tuple(shape)),
                                    on_replay=self._bn_replay)
         if return_logits:
             return logits
@@ -83,7 +83,7 @@ class RCNetModel(object):
         """host-side bookkeeping of one replayed forward: the BatchNorm layers' num_batches_tracked counters (net_utils._BNCounter)"""
         for net in (self._unwrap(self.encoder), self._unwrap(self.decoder)):
             for m in net.modules():
-                if getattr(m, 'use_batch_norm', False) and hasattr(m, '_nbt_pending') and m.training:
+                if hasattr(m, '_nbt_pending') and m._bn_counts():
                     m._nbt_pending += 1
 
     def parameters(self):

@@ -167,15 +167,9 @@ class GraphedTrainStep(object):
 
     def __new__(cls, model, optimizer, batch, cfg=ZJU_SML_CONFIG, reducer=None, outlier=None, warmup=2, loss_scale=1.0):
         from .rcnet_main import GraphedStep
-        from .midas.efficientnet_lite3 import _Counted
-        counted = [m for m in model.modules() if isinstance(m, _Counted)]
 
         def bump(delta):
-            if model.training:
-                for m in counted:
-                    m._pending += delta
-                model._first_pending += delta
-                model.pretrained.layer1._stem_pending = getattr(model.pretrained.layer1, "_stem_pending", 0) + delta
+            model._bn_replay(delta)      # per BatchNorm: only layers that run in training mode count a batch
         buffers = [b for b in model.buffers() if b.is_floating_point()]
         step = GraphedStep(lambda: forward_loss(model, batch, cfg, outlier), optimizer, reducer, warmup, bump, buffers, loss_scale)
         step.static_batch = tuple(batch)      # GraphedStep.load_batch(new_batch) copies a new batch into these before a replay
