@@ -481,6 +481,30 @@ int rd_grad_finite_check(const float* grad, int64_t n, int32_t* flag, void* stre
 int rd_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                          float beta2, float eps, float weight_decay, int64_t step, float grad_scale, const int32_t* skip_flag, void* stream);
 int rd_adam_skip_count(int32_t* flag, void* stream);
+/* torch.optim.Adam's parameter groups (the reference builds its optimizer from a list of group dictionaries: RCNet/rcnet_main.py:233-238) in
+ * ONE launch over the arena: group g covers elements [end[g-1], end[g]) (end[-1] = 0) and is updated with its own constants and step count.
+ * Decoupled weight decay (flags bit 0; torch's AdamW) multiplies the parameter by 1 - lr * weight_decay first and adds nothing to the
+ * gradient; the coupled form adds weight_decay * param to it, as rd_adam_step.  An inactive group (flags bit 1: none of its parameters has a
+ * gradient this step) is neither read for update nor written.  The table is HOST memory, read during the enqueue only: it travels to the
+ * kernel by value in the kernel arguments, so no copy precedes the launch and the launch can be captured.  Ends are strictly ascending,
+ * interior ends multiples of 4 elements (the 16-byte vectors never straddle two groups), the last end equals n; every active group has
+ * step >= 1.  skip_flag (may be NULL) as in rd_adam_step_guarded: the whole launch writes nothing while flag[0] is set. */
+#define RD_ADAM_MAX_GROUPS 8
+#define RD_ADAM_DECOUPLED 1
+#define RD_ADAM_INACTIVE 2
+typedef struct rd_adam_groups {
+  int32_t count;
+  int32_t flags[RD_ADAM_MAX_GROUPS];
+  int64_t end[RD_ADAM_MAX_GROUPS];
+  int64_t step[RD_ADAM_MAX_GROUPS];
+  float lr[RD_ADAM_MAX_GROUPS];
+  float beta1[RD_ADAM_MAX_GROUPS];
+  float beta2[RD_ADAM_MAX_GROUPS];
+  float eps[RD_ADAM_MAX_GROUPS];
+  float weight_decay[RD_ADAM_MAX_GROUPS];
+} rd_adam_groups;
+int rd_adam_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const rd_adam_groups* groups,
+                        float grad_scale, const int32_t* skip_flag, void* stream);
 
 /* ---- routing options: kernel-selection switches for tests and A/B tools (the product path reads no environment variable).  Names and
  * ranges: kOpts in csrc/rd_api.cpp (e.g. "conv3x3_min_blocks", "frag_v128", "frag32_v128", "wgrad_tr_tw"); values are clamped; an unknown

@@ -98,6 +98,18 @@ class LnGradItem(ctypes.Structure):
                 ("C", ctypes.c_int32), ("nparts", ctypes.c_int32), ("accumulate", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+RD_ADAM_MAX_GROUPS = 8
+ADAM_DECOUPLED, ADAM_INACTIVE = 1, 2
+
+
+class AdamGroups(ctypes.Structure):
+    """rd_adam_groups: the parameter-group table of rd_adam_step_groups (host memory, read during the enqueue only)."""
+    _fields_ = [("count", ctypes.c_int32), ("flags", ctypes.c_int32 * RD_ADAM_MAX_GROUPS), ("end", ctypes.c_int64 * RD_ADAM_MAX_GROUPS),
+                ("step", ctypes.c_int64 * RD_ADAM_MAX_GROUPS), ("lr", ctypes.c_float * RD_ADAM_MAX_GROUPS),
+                ("beta1", ctypes.c_float * RD_ADAM_MAX_GROUPS), ("beta2", ctypes.c_float * RD_ADAM_MAX_GROUPS),
+                ("eps", ctypes.c_float * RD_ADAM_MAX_GROUPS), ("weight_decay", ctypes.c_float * RD_ADAM_MAX_GROUPS)]
+
+
 _SCALARS = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
     "float": ctypes.c_float, "double": ctypes.c_double,
@@ -111,6 +123,8 @@ def _ctype(decl):
         base = decl.split("*")[0].replace("const", "").strip()
         if base == "rd_conv_desc":
             return ctypes.POINTER(ConvDesc)
+        if base == "rd_adam_groups":
+            return ctypes.POINTER(AdamGroups)
         if base == "char":
             return ctypes.c_char_p
         return ctypes.c_void_p

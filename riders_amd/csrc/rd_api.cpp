@@ -885,6 +885,43 @@ int rd_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n
   rd::launch_adam(p, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), gscale, S(stream), skip_flag);
   return done("rd_adam_step_guarded");
 }
+int rd_adam_step_groups(float* p, const float* g, float* m, float* v, int64_t n, const rd_adam_groups* groups, float gscale,
+                        const int32_t* skip_flag, void* stream) {
+  if (!p || !g || !m || !v || !groups) return fail("adam_groups: null pointer");
+  const int count = groups->count;
+  if (count < 1 || count > RD_ADAM_MAX_GROUPS) return fail("adam_groups: count must be 1..%d (got %d)", RD_ADAM_MAX_GROUPS, count);
+  rd::AdamGroupTable t;
+  t.inactive_mask = 0;
+  int64_t prev = 0;
+  for (int k = 0; k < count; k++) {
+    const int64_t e = groups->end[k];
+    if (e <= prev) return fail("adam_groups: group ends must be strictly ascending (end[%d] = %lld)", k, (long long)e);
+    if (k + 1 < count && (e & 3)) return fail("adam_groups: interior end[%d] = %lld is not a multiple of 4", k, (long long)e);
+    prev = e;
+  }
+  if (prev != n) return fail("adam_groups: the last end (%lld) must equal n (%lld)", (long long)prev, (long long)n);
+  for (int k = 0; k < RD_ADAM_MAX_GROUPS; k++) {
+    const bool live = k < count;
+    const bool inactive = live && (groups->flags[k] & RD_ADAM_INACTIVE);
+    if (live && !inactive && groups->step[k] < 1) return fail("adam_groups: step[%d] must be >= 1", k);
+    t.end[k] = live ? groups->end[k] : n;
+    if (inactive) t.inactive_mask |= 1 << k;
+    if (!live || inactive) {
+      t.step_size[k] = t.b1[k] = t.b2[k] = t.eps[k] = t.wd[k] = 0.f; t.decay[k] = t.bc2_sqrt[k] = 1.f;
+      continue;
+    }
+    const float lr = groups->lr[k], b1 = groups->beta1[k], b2 = groups->beta2[k], wd = groups->weight_decay[k];
+    const bool decoupled = groups->flags[k] & RD_ADAM_DECOUPLED;
+    double bc1 = 1.0 - pow((double)b1, (double)groups->step[k]), bc2 = 1.0 - pow((double)b2, (double)groups->step[k]);
+    t.step_size[k] = lr / (float)bc1;      // rd_adam_step's kernel divides the same two fp32 values
+    t.b1[k] = b1; t.b2[k] = b2; t.eps[k] = groups->eps[k];
+    t.wd[k] = decoupled ? 0.f : wd;
+    t.decay[k] = decoupled ? (float)(1.0 - (double)lr * (double)wd) : 1.f;
+    t.bc2_sqrt[k] = (float)sqrt(bc2);
+  }
+  rd::launch_adam_groups(p, g, m, v, n, t, gscale, S(stream), skip_flag);
+  return done("rd_adam_step_groups");
+}
 int rd_adam_skip_count(int32_t* flag, void* stream) {
   if (!flag) return fail("adam_skip_count: null pointer");
   rd::launch_adam_skip_count(flag, S(stream));

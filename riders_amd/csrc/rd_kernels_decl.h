@@ -192,6 +192,20 @@ void launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float 
                  float wd, float bc1, float bc2, float gscale, hipStream_t st, const int* skip = nullptr);
 void launch_grad_finite(const float* g, int64_t n, int* flag, hipStream_t st);
 void launch_adam_skip_count(int* flag, hipStream_t st);
+// rd_adam_step_groups: what the kernel needs of the public table, passed BY VALUE in the kernel arguments (rd_api.cpp fills it: bias
+// corrections in double, ends past `count` = n so that the group of an element is the number of ends at or below it)
+constexpr int kAdamMaxGroups = 8;
+struct AdamGroupTable {
+  int64_t end[kAdamMaxGroups];
+  int inactive_mask;                    // bit g: group g is neither read nor written
+  float step_size[kAdamMaxGroups];      // lr / bias correction 1
+  float b1[kAdamMaxGroups], b2[kAdamMaxGroups], eps[kAdamMaxGroups];
+  float wd[kAdamMaxGroups];             // coupled weight decay (0 for a decoupled group)
+  float decay[kAdamMaxGroups];          // 1 - lr * weight_decay for a decoupled group, 1 otherwise
+  float bc2_sqrt[kAdamMaxGroups];
+};
+void launch_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, float gscale, hipStream_t st,
+                        const int* skip);
 
 
 // rd_dwconv.hip

@@ -55,6 +55,101 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// ---- parameter groups (torch.optim.Adam's list of group dictionaries, RCNet/rcnet_main.py:233-238) in one launch --------------------------
+// The table arrives by value in the kernel arguments and is only ever indexed with compile-time constants (a runtime index would send it to
+// scratch): the group of an element is the number of group ends at or below it, a group's constant is an unrolled select.  Both are scalar
+// work when the element index is block-uniform, which it is for the first and last element of a block's 1024-element chunk, and both are
+// done only when a block's chunk leaves the group its previous chunk was in.
+__device__ __forceinline__ int adam_group_of(const AdamGroupTable& t, int64_t e) {
+  int g = 0;
+#pragma unroll
+  for (int k = 0; k < kAdamMaxGroups - 1; k++) g += e >= t.end[k] ? 1 : 0;      // ends past the last group equal n > e
+  return g;
+}
+__device__ __forceinline__ float adam_sel(const float (&a)[kAdamMaxGroups], int g) {
+  float r = a[0];
+#pragma unroll
+  for (int k = 1; k < kAdamMaxGroups; k++) r = g == k ? a[k] : r;
+  return r;
+}
+__device__ __forceinline__ int64_t adam_end(const AdamGroupTable& t, int g) {
+  int64_t r = t.end[0];
+#pragma unroll
+  for (int k = 1; k < kAdamMaxGroups; k++) r = g == k ? t.end[k] : r;
+  return r;
+}
+struct AdamConsts { float step, b1, b2, eps, wd, decay, bc2_sqrt; };
+__device__ __forceinline__ AdamConsts adam_consts(const AdamGroupTable& t, int g) {
+  AdamConsts c;
+  c.step = adam_sel(t.step_size, g); c.b1 = adam_sel(t.b1, g); c.b2 = adam_sel(t.b2, g); c.eps = adam_sel(t.eps, g);
+  c.wd = adam_sel(t.wd, g); c.decay = adam_sel(t.decay, g); c.bc2_sqrt = adam_sel(t.bc2_sqrt, g);
+  return c;
+}
+// adam_kernel's arithmetic with one group's constants; decoupled decay scales p first (decay = 1 and p * 1 = p for a coupled group)
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const AdamConsts& c, float gscale) {
+  float pd = p * c.decay;
+  float gr = g * gscale + c.wd * pd;
+  m = c.b1 * m + (1.f - c.b1) * gr;
+  v = c.b2 * v + (1.f - c.b2) * gr * gr;
+  p = pd - c.step * m / (sqrtf(v) / c.bc2_sqrt + c.eps);
+}
+__device__ __forceinline__ void adam_update4(float* p, const float* g, float* m, float* v, int64_t i4, const AdamConsts& c, float gscale) {
+  float pp[4], gg[4], mm[4], vv[4];
+  ld4(p + (i4 << 2), pp); ld4(g + (i4 << 2), gg); ld4(m + (i4 << 2), mm); ld4(v + (i4 << 2), vv);
+#pragma unroll
+  for (int e = 0; e < 4; e++) adam_update(pp[e], gg[e], mm[e], vv[e], c, gscale);
+  st4(p + (i4 << 2), pp); st4(m + (i4 << 2), mm); st4(v + (i4 << 2), vv);
+}
+
+__global__ __launch_bounds__(256) void adam_groups_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
+    float gscale, const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  const int64_t n4 = n >> 2;
+  // one chunk = the 256 consecutive 16-byte vectors a block handles per grid-stride iteration.  A block's chunks ascend: the outer loop looks the
+  // group of a chunk up, the inner loop is adam_kernel's loop over the block's chunks that lie wholly inside that group (one scalar compare each)
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t c0 = (int64_t)blockIdx.x * blockDim.x;
+  while (c0 < n4) {
+    const int64_t last = (c0 + blockDim.x < n4 ? c0 + blockDim.x : n4) - 1;
+    const int glo = adam_group_of(t, c0 << 2), ghi = adam_group_of(t, last << 2);
+    if (glo != ghi) {      // a group boundary inside the chunk: every vector looks its own group up (interior ends are multiples of 4)
+      const int64_t i = c0 + threadIdx.x;
+      if (i < n4) {
+        const int gi = adam_group_of(t, i << 2);
+        if (!((t.inactive_mask >> gi) & 1)) adam_update4(p, g, m, v, i, adam_consts(t, gi), gscale);
+      }
+      c0 += stride;
+      continue;
+    }
+    // chunks starting at or below `bound` lie wholly inside the group (the last group ends with the arena's last, possibly partial, chunk)
+    const int64_t lim4 = adam_end(t, glo) >> 2;
+    const int64_t bound = lim4 >= n4 ? n4 - 1 : lim4 - (int64_t)blockDim.x;
+    if ((t.inactive_mask >> glo) & 1) {      // nothing of an inactive group is read
+      do c0 += stride; while (c0 <= bound);
+      continue;
+    }
+    const AdamConsts c = adam_consts(t, glo);
+    do {
+      const int64_t i = c0 + threadIdx.x;
+      if (i < n4) adam_update4(p, g, m, v, i, c, gscale);
+      c0 += stride;
+    } while (c0 <= bound);
+  }
+  // the scalar tail belongs to the last group
+  const int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const int gt = adam_group_of(t, n4 << 2);
+    if (!((t.inactive_mask >> gt) & 1)) adam_update(p[i], g[i], m[i], v[i], adam_consts(t, gt), gscale);
+  }
+}
+
+void launch_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, float gscale, hipStream_t st,
+                        const int* skip) {
+  unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 1024), 2048));
+  hipLaunchKernelGGL(adam_groups_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, t, gscale, skip);
+}
+
 void launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                  float bc1, float bc2_sqrt, float gscale, hipStream_t st, const int* skip) {
   unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 1024), 2048));

@@ -13,28 +13,62 @@ torch skips a parameter whose `.grad` is None (no moment update, no step increme
 that no backward kernel wrote since `zero_grad()` is left out of the step.  A slot that has NEVER been written
 holds zero gradient and zero moments, for which the update is exactly zero, so the common case -- the reference's
 never-used `projection` convolutions (utils/net_utils.py:300-307) -- still runs as one launch over the arena.
+
+Parameter groups.  The reference's three training loops pass a list of group dictionaries
+(`[{'params': parameters, 'weight_decay': w_weight_decay}]`, RCNet/rcnet_main.py:233-238); that form, per-group `lr` / `betas` / `eps` /
+`weight_decay` and torch 2.10's `decoupled_weight_decay` (what AdamW is) are accepted.  The arena is laid out group after group, so a group is
+one contiguous range and rd_adam_step_groups updates all of them in one launch (the group table travels in the kernel arguments).  One group
+with coupled decay -- every optimizer built the flat way -- launches rd_adam_step exactly as before.
 """
 import ctypes
 
 import torch
 
-from . import engine
+from . import _lib, engine
 
+_HYPER = ('lr', 'betas', 'eps', 'weight_decay', 'decoupled_weight_decay')
 _GROUP_DEFAULTS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
                        decoupled_weight_decay=False)
 
 
 class FlatAdam(object):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False):
         params = [p for p in params]
         if len(params) == 0:
-            raise ValueError("FlatAdam got an empty parameter list")
+            raise ValueError("optimizer got an empty parameter list")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay)
+        if not isinstance(params[0], dict):      # the flat form: one group
+            params = [dict(params=params)]
+        if len(params) > _lib.RD_ADAM_MAX_GROUPS:
+            raise ValueError("FlatAdam supports at most %d parameter groups (got %d)" % (_lib.RD_ADAM_MAX_GROUPS, len(params)))
+        self.param_groups, seen = [], set()
+        for src in params:
+            if not isinstance(src, dict):
+                raise TypeError("param group must be a dict")
+            ps = src['params']
+            ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+            if len(ps) == 0:
+                raise ValueError("optimizer got an empty parameter list")
+            if any(id(p) in seen for p in ps) or len(set(id(p) for p in ps)) != len(ps):
+                raise ValueError("some parameters appear in more than one parameter group")
+            seen.update(id(p) for p in ps)
+            if bool(src.get('amsgrad', False)) or bool(src.get('maximize', False)):
+                raise ValueError("amsgrad / maximize Adam are not supported (the reference uses neither)")
+            g = {k: v for k, v in src.items() if k != 'params'}
+            for k, v in defaults.items():
+                g.setdefault(k, v)
+            g['params'] = ps
+            self.param_groups.append(g)
+        params = [p for g in self.param_groups for p in g['params']]      # torch's state indices: the groups in order
         dev = params[0].device
         for p in params:
             if p.dtype != torch.float32 or p.device != dev:
                 raise ValueError("FlatAdam needs fp32 parameters on one device")
         self.params = params
-        self.param_groups = [dict(params=params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
+        self._group_slots, k = [], 0      # [first, end) parameter indices of every group
+        for g in self.param_groups:
+            self._group_slots.append((k, k + len(g['params'])))
+            k += len(g['params'])
         # 16-byte aligned slots so the vectorised kernel and RCCL see aligned slices
         self.offsets, n = [], 0
         for p in params:
@@ -137,6 +171,9 @@ class FlatAdam(object):
                 engine._chk(engine.L().rd_cast(engine._p(gc), engine._p(view), gc.numel(), engine.rd_of(gc), 0, 1.0,
                                                engine._stream(gc)), "rd_cast")
 
+    def add_param_group(self, param_group):
+        raise NotImplementedError("FlatAdam: the arena is sized at construction; pass every parameter group to the constructor")
+
     def _launch(self, start, end, step):
         g = self.param_groups[0]
         sl = slice(start, end)
@@ -149,6 +186,65 @@ class FlatAdam(object):
         else:
             rc = engine._tb("optimizer", 28 * (end - start), lambda: engine.L().rd_adam_step(*args, st), "adam")
         engine._chk(rc, "rd_adam_step")
+
+    def _group_end(self, gi):
+        """arena element where group gi ends"""
+        j = self._group_slots[gi][1]
+        return self.offsets[j] if j < len(self.params) else self.numel
+
+    def _launch_groups(self, start, end, entries):
+        """One rd_adam_step_groups launch over arena elements [start, end).  entries: [(param group, end element, step or None = inactive)]."""
+        t = _lib.AdamGroups()
+        t.count = len(entries)
+        live = 0
+        prev = start
+        for k, (g, e, step) in enumerate(entries):
+            t.end[k] = e - start
+            t.flags[k] = (_lib.ADAM_DECOUPLED if g['decoupled_weight_decay'] else 0) | (_lib.ADAM_INACTIVE if step is None else 0)
+            t.step[k] = 1 if step is None else step
+            t.lr[k], t.beta1[k], t.beta2[k], t.eps[k], t.weight_decay[k] = g['lr'], g['betas'][0], g['betas'][1], g['eps'], g['weight_decay']
+            live += 0 if step is None else e - prev
+            prev = e
+        sl = slice(start, end)
+        ptrs = (engine._p(self.flat_param[sl]), engine._p(self.flat_grad[sl]), engine._p(self.exp_avg[sl]), engine._p(self.exp_avg_sq[sl]))
+        skip = engine._p(self._overflow) if self._overflow is not None else None
+        st = engine._stream(self.flat_param)
+        rc = engine._tb("optimizer", 28 * live, lambda: engine.L().rd_adam_step_groups(*ptrs, end - start, t, ctypes.c_float(self.grad_scale / self.loss_scale),
+                                                                                       skip, st), "adam")
+        engine._chk(rc, "rd_adam_step_groups")
+
+    def _step_groups(self):
+        """Several groups, or decoupled decay: ONE launch when every group is inactive (no slot written since zero_grad()) or uniform (its written
+        slots share a step count, and every slot not written this step has never been written while the group decays nothing: zero gradient and
+        zero moments, the update is exactly zero); otherwise one one-group launch per run of consecutive written slots that share a step count,
+        runs split at group boundaries."""
+        n = len(self.params)
+        entries, one = [], True
+        for gi, (g, (a, b)) in enumerate(zip(self.param_groups, self._group_slots)):
+            live = set(self.steps[i] for i in range(a, b) if self._touched[i])
+            if not live:
+                entries.append((g, self._group_end(gi), None))
+                continue
+            idle_ok = g['weight_decay'] == 0 and not any(self._ever[i] for i in range(a, b) if not self._touched[i])
+            if len(live) != 1 or not (idle_ok or all(self._touched[a:b])):
+                one = False
+                break
+            entries.append((g, self._group_end(gi), live.pop()))
+        if one:
+            self._launch_groups(0, self.numel, entries)
+            return
+        for gi, (g, (a, b)) in enumerate(zip(self.param_groups, self._group_slots)):
+            i = a
+            while i < b:
+                if not self._touched[i]:
+                    i += 1
+                    continue
+                j = i
+                while j + 1 < b and self._touched[j + 1] and self.steps[j + 1] == self.steps[i]:
+                    j += 1
+                end = self.offsets[j + 1] if j + 1 < n else self.numel
+                self._launch_groups(self.offsets[i], end, [(g, end, self.steps[i])])
+                i = j + 1
 
     def step(self):
         self._gather_foreign_grads()
@@ -166,23 +262,26 @@ class FlatAdam(object):
                 self._overflow = torch.zeros(2, dtype=torch.int32, device=self.flat_param.device)
             engine._chk(engine.L().rd_grad_finite_check(engine._p(self.flat_grad), self.numel, engine._p(self._overflow),
                                                         engine._stream(self.flat_param)), "rd_grad_finite_check")
-        # one launch when every slot is either written this step (all at the same step count) or has never been written (zero gradient and
-        # zero moments: the update is exactly zero); otherwise one launch per run of consecutive written slots that share a step count
-        uniform = len(set(live)) == 1 and all(t or not e for t, e in zip(self._touched, self._ever)) and self.param_groups[0]['weight_decay'] == 0
-        if uniform:
-            self._launch(0, self.numel, live[0])
+        if len(self.param_groups) > 1 or self.param_groups[0]['decoupled_weight_decay']:
+            self._step_groups()
         else:
-            i = 0
-            while i < n:
-                if not self._touched[i]:
-                    i += 1
-                    continue
-                j = i
-                while j + 1 < n and self._touched[j + 1] and self.steps[j + 1] == self.steps[i]:
-                    j += 1
-                end = self.offsets[j + 1] if j + 1 < n else self.numel
-                self._launch(self.offsets[i], end, self.steps[i])
-                i = j + 1
+            # one launch when every slot is either written this step (all at the same step count) or has never been written (zero gradient and
+            # zero moments: the update is exactly zero); otherwise one launch per run of consecutive written slots that share a step count
+            uniform = len(set(live)) == 1 and all(t or not e for t, e in zip(self._touched, self._ever)) and self.param_groups[0]['weight_decay'] == 0
+            if uniform:
+                self._launch(0, self.numel, live[0])
+            else:
+                i = 0
+                while i < n:
+                    if not self._touched[i]:
+                        i += 1
+                        continue
+                    j = i
+                    while j + 1 < n and self._touched[j + 1] and self.steps[j + 1] == self.steps[i]:
+                        j += 1
+                    end = self.offsets[j + 1] if j + 1 < n else self.numel
+                    self._launch(self.offsets[i], end, self.steps[i])
+                    i = j + 1
         if guarded:
             engine._chk(engine.L().rd_adam_skip_count(engine._p(self._overflow), engine._stream(self.flat_param)), "rd_adam_skip_count")
         engine.refresh_packed(self._owner)   # one launch re-packs every cached MFMA operand of the rewritten parameters (this optimizer's only)
@@ -190,7 +289,7 @@ class FlatAdam(object):
     # ------------------------------------------------------------------ checkpoint interchange with torch.optim.Adam
     def state_dict(self):
         """torch.optim.Adam's layout: per-parameter `step` / `exp_avg` / `exp_avg_sq` (copies sliced out of the arena) for every parameter
-        that has received a gradient, and one param group listing parameter indices."""
+        that has received a gradient, and every param group with its hyperparameters and its parameter indices."""
         state = {}
         engine.check_roi_overflow()   # (the host waits here anyway) a checkpoint must not be written from NaN-poisoned moments
         self.reconcile_skipped()      # `step` = updates actually applied (fp16 mode: not the skipped ones)
@@ -200,11 +299,14 @@ class FlatAdam(object):
             state[i] = dict(step=torch.tensor(float(self.steps[i])),
                             exp_avg=self.exp_avg[o:o + p.numel()].view(p.shape).clone(),
                             exp_avg_sq=self.exp_avg_sq[o:o + p.numel()].view(p.shape).clone())
-        g = {k: v for k, v in self.param_groups[0].items() if k != 'params'}
-        for k, v in _GROUP_DEFAULTS.items():
-            g.setdefault(k, v)
-        g['params'] = list(range(len(self.params)))
-        return dict(state=state, param_groups=[g])
+        groups = []
+        for src, (a, b) in zip(self.param_groups, self._group_slots):
+            g = {k: v for k, v in src.items() if k != 'params'}
+            for k, v in _GROUP_DEFAULTS.items():
+                g.setdefault(k, v)
+            g['params'] = list(range(a, b))      # consecutive indices running through the groups, as torch writes them
+            groups.append(g)
+        return dict(state=state, param_groups=groups)
 
     def load_state_dict(self, sd):
         """Accepts a torch.optim.Adam state_dict (the reference's `radarnet_optimizer_state_dict`), this class's own output, and the
@@ -218,9 +320,11 @@ class FlatAdam(object):
             self._skips_reconciled = self.skipped_steps()
             return
         groups = sd['param_groups']
+        if len(groups) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups (%d, the optimizer has %d)" % (len(groups), len(self.param_groups)))
+        if any(len(g['params']) != b - a for g, (a, b) in zip(groups, self._group_slots)):
+            raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
         order = [i for g in groups for i in g['params']]
-        if len(order) != len(self.params):
-            raise ValueError("loaded state dict has %d parameters, the optimizer has %d" % (len(order), len(self.params)))
         if any(bool(g.get('amsgrad', False)) or bool(g.get('maximize', False)) for g in groups):
             raise ValueError("amsgrad / maximize Adam states are not supported (the reference uses neither)")
         with torch.no_grad():
@@ -241,7 +345,15 @@ class FlatAdam(object):
                 self._ever[pos] = True
         # the loaded `step` values are updates actually applied: skips counted on the device so far belong to the state that was replaced
         self._skips_reconciled = self.skipped_steps()
-        g0 = {k: v for k, v in groups[0].items() if k in ('lr', 'betas', 'eps', 'weight_decay')}
-        if 'betas' in g0:
-            g0['betas'] = tuple(g0['betas'])
-        self.param_groups[0].update(g0)
+        for mine, theirs in zip(self.param_groups, groups):
+            hp = {k: v for k, v in theirs.items() if k in _HYPER}
+            if 'betas' in hp:
+                hp['betas'] = tuple(hp['betas'])
+            mine.update(hp)
+
+
+class FlatAdamW(FlatAdam):
+    """torch.optim.AdamW: FlatAdam with decoupled weight decay and AdamW's default weight_decay = 1e-2."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super(FlatAdamW, self).__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=True)
