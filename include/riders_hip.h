@@ -445,6 +445,24 @@ int rd_augment_vflip_boxes(float* boxes, int32_t B, int32_t K, const float* para
 int rd_crop_patches(const float* gt_padded, const float* points, float* crops, int32_t B, int32_t K, int32_t Hp, int32_t Wp, int32_t ph,
                     int32_t pw, void* stream);
 
+/* ---- Scale Map Learner batch augmentation -- data/UTV_dataset.py:20-120, :195-217 (crop + resize back, flip, radar noise) ------------------
+   params: [B][8] floats = (do_crop, x_start, y_start, do_flip, do_noise, 0, 0, 0), drawn by the host in the reference's order.
+   rd_sml_augment_geom: ONE launch over image (B,3,H,W) and the five (B,1,H,W) maps (rcnet / rcnet_out NULL together: no such map); output pixel
+   (y, x) takes column u = do_flip ? W-1-x : x, a copy of (y, u) or the bilinear sample at (y, u) of the window [y_start, y_start + crop_h) x
+   [x_start, x_start + crop_w) resized to (H, W) (cv2.resize, INTER_LINEAR, restated: horizontal then vertical pass in float32, taps clamped at
+   the window's edges).  xtab [W][2] / ytab [H][2] floats = (first tap relative to the window, weight f of the second tap), computed once by
+   the host for (crop size, H, W); crop_h = crop_w = 0 (tables may be NULL): no sample is cropped, do_crop is not looked at.  Starts and taps
+   are clamped into the window, the window into the plane.  Outputs must not alias inputs or each other: equal pointers are refused (rc < 0). */
+int rd_sml_augment_geom(const float* image, const float* mono, const float* radar, const float* gt, const float* sparse_gt, const float* rcnet,
+                        float* image_out, float* mono_out, float* radar_out, float* gt_out, float* sparse_gt_out, float* rcnet_out, int32_t B, int32_t H,
+                        int32_t W, const float* params, const float* xtab, const float* ytab, int32_t crop_h, int32_t crop_w, void* stream);
+/* :212-217 in place on the augmented radar (B,1,H,W): in a sample with do_noise the positive pixel of row-major rank r becomes
+   (float)((double)radar + noise[offsets[b] + r]); offsets int32 [B+1] into noise (n_noise doubles).  Nothing at or beyond offsets[b+1], or
+   outside the buffer, is read: a positive pixel whose rank is out of range is left alone, and *flag (device int32, sticky, zeroed by the
+   caller) becomes 1 when a flagged sample's count of positive pixels differs from its row's length in either direction. */
+int rd_sml_augment_noise(float* radar, int32_t B, int32_t H, int32_t W, const float* params, const double* noise, const int32_t* offsets,
+                         int64_t n_noise, int32_t* flag, void* stream);
+
 /* ---- offline projection + scatter -- data/preprocess/project_transform.py:67-97, pointcloud_project_zju.py:57-76,81-103 ------------------
    points (n, stride >= 3) float32 xyz; t_camera_pcl, projection: 4x4 row-major float64 (device); depth_map (H,W) = max(depth, 1) of the
    NEAREST point projecting to each pixel, 0 elsewhere (bit-exact, order independent); kept_points (n,3) = (u, v, depth) of the points

@@ -825,6 +825,36 @@ int rd_augment_flip_labels(const float* labels_in, float* labels_out, int32_t B,
   rd::launch_augment_flip_labels(labels_in, labels_out, B, K, ph, pw, boxes, params, n_width, S(stream));
   return done("rd_augment_flip_labels");
 }
+int rd_sml_augment_geom(const float* image, const float* mono, const float* radar, const float* gt, const float* sparse_gt, const float* rcnet,
+                        float* image_out, float* mono_out, float* radar_out, float* gt_out, float* sparse_gt_out, float* rcnet_out, int32_t B, int32_t H,
+                        int32_t W, const float* params, const float* xtab, const float* ytab, int32_t crop_h, int32_t crop_w, void* stream) {
+  rd::SmlAugPlanes pl = {{image, mono, radar, gt, sparse_gt, rcnet}, {image_out, mono_out, radar_out, gt_out, sparse_gt_out, rcnet_out}};
+  for (int k = 0; k < 5; k++)
+    if (!pl.in[k] || !pl.out[k]) return fail("sml_augment_geom: null plane %d", k);
+  if ((rcnet == nullptr) != (rcnet_out == nullptr)) return fail("sml_augment_geom: rcnet and rcnet_out are given or left out together");
+  if (!params || B <= 0 || H <= 0 || W <= 0) return fail("sml_augment_geom: bad args");
+  if ((int64_t)B * 3 * H * W >= (int64_t)1 << 31) return fail("sml_augment_geom: too many pixels");
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++)
+      if (pl.in[i] && pl.in[i] == pl.out[j]) return fail("sml_augment_geom: output %d aliases input %d (a flipped row is read after it would be written)", j, i);
+  for (int i = 0; i < 6; i++)
+    for (int j = i + 1; j < 6; j++)
+      if (pl.out[i] && pl.out[i] == pl.out[j]) return fail("sml_augment_geom: outputs %d and %d are the same buffer", i, j);
+  if (crop_h || crop_w) {
+    if (crop_h < 1 || crop_h > H || crop_w < 1 || crop_w > W) return fail("sml_augment_geom: crop %d x %d does not fit %d x %d", crop_h, crop_w, H, W);
+    if (!xtab || !ytab) return fail("sml_augment_geom: a crop size needs both tap tables");
+  }
+  rd::launch_sml_augment_geom(pl, B, H, W, params, xtab, ytab, crop_h, crop_w, S(stream));
+  return done("rd_sml_augment_geom");
+}
+int rd_sml_augment_noise(float* radar, int32_t B, int32_t H, int32_t W, const float* params, const double* noise, const int32_t* offsets,
+                         int64_t n_noise, int32_t* flag, void* stream) {
+  if (!radar || !params || !offsets || !flag || B <= 0 || H <= 0 || W <= 0) return fail("sml_augment_noise: bad args");
+  if (n_noise < 0 || n_noise >= (int64_t)1 << 31 || (n_noise > 0 && !noise)) return fail("sml_augment_noise: bad noise length");
+  if ((int64_t)H * W >= (int64_t)1 << 30) return fail("sml_augment_noise: too many pixels per sample");
+  rd::launch_sml_augment_noise(radar, B, H * W, params, noise, offsets, (int)n_noise, flag, S(stream));
+  return done("rd_sml_augment_noise");
+}
 int rd_augment_vflip_boxes(float* boxes, int32_t B, int32_t K, const float* params, float n_height, void* stream) {
   if (!boxes || !params || B <= 0) return fail("augment_vflip_boxes: bad args");
   if (K < 4) return fail("augment_vflip_boxes: the reference indexes boxes 1 and 3 of each sample (rcnet_transforms.py:213-217): K >= 4");

@@ -183,6 +183,11 @@ void launch_augment_image(const float* image, int B, int H, int W, const float* 
 void launch_augment_flip_labels(const float* lin, float* lout, int B, int K, int ph, int pw, float* boxes, const float* params, float n_width, hipStream_t st);
 void launch_crop_patches(const float* gt, const float* points, float* crops, int B, int K, int Hp, int Wp, int ph, int pw, hipStream_t st);
 
+// rd_sml_augment.hip: image, mono, radar, gt, sparse gt, rcnet (in[5] and out[5] NULL together: no rcnet map)
+struct SmlAugPlanes { const float* in[6]; float* out[6]; };
+void launch_sml_augment_geom(const SmlAugPlanes& pl, int B, int H, int W, const float* params, const float* xtab, const float* ytab, int nh, int nw, hipStream_t st);
+void launch_sml_augment_noise(float* radar, int B, int HW, const float* params, const double* noise, const int* off, int n_noise, int* flag, hipStream_t st);
+
 void launch_tri_raster(const int* tri, const int* prow, const int* pcol, const double* values, int M, int H, int W, double fill, int* owner, double* out, hipStream_t st);
 void launch_nearest_knot(const int* prow, const int* pcol, const double* values, int K, int H, int W, double fill, double* out, hipStream_t st);
 void launch_project_scatter(const float* pts, int n, int stride, const double* T, const double* P, int H, int W, double dmin, double dmax, float* depth_map, float* kept, int* nkept, hipStream_t st);
