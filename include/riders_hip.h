@@ -553,7 +553,8 @@ int64_t rd_comm_pending(void* comm);
 
 /* ==== Scale Map Learner (MiDaS-small) ================================================================================ */
 /* depthwise convolution of the tf_efficientnet_lite3 backbone (modules/midas/blocks.py:44-64; torch.hub, third-party):
- * w = OIHW fp32 with I = 1; p = TF-"SAME" leading pad; partial [rd_dw_rows][C][k*k] */
+ * w = OIHW fp32 with I = 1; p = TF-"SAME" leading pad; partial [rd_dw_rows][C][k*k].  Every size >= 1, 1 <= k <= 5, s >= 1 and
+ * 0 <= p < k, or the call is refused ("bad args") before anything is launched; rd_bilinear_* refuse a size < 1 likewise */
 int32_t rd_dw_rows(int64_t pixels, int32_t C);
 int rd_dwconv_fwd(const void* x, const float* w, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, int32_t k,
                   int32_t s, int32_t p, int32_t dtype, void* stream);

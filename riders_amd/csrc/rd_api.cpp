@@ -960,29 +960,35 @@ int rd_adam_skip_count(int32_t* flag, void* stream) {
 
 
 // ---- Scale Map Learner ------------------------------------------------------------------------------------------------
+// geometry every depthwise / bilinear entry point refuses before it launches: a size < 1; a stride < 1 (the data gradient takes % s); a
+// leading pad outside [0, k)
+static bool sizes_ok(int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW) { return N >= 1 && H >= 1 && W >= 1 && C >= 1 && OH >= 1 && OW >= 1; }
+static bool dw_geom_ok(int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, int32_t k, int32_t s, int32_t p) {
+  return sizes_ok(N, H, W, C, OH, OW) && k >= 1 && k <= 5 && s >= 1 && p >= 0 && p < k;
+}
 int32_t rd_dw_rows(int64_t pixels, int32_t C) { return rd::dw_rows(pixels, C); }
 int rd_dwconv_fwd(const void* x, const float* w, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, int32_t k,
                   int32_t s, int32_t p, int32_t dtype, void* stream) {
-  if (!x || !w || !y || !dt_ok(dtype) || k > 5 || k < 1) return fail("dwconv_fwd: bad args");
+  if (!x || !w || !y || !dt_ok(dtype) || !dw_geom_ok(N, H, W, C, OH, OW, k, s, p)) return fail("dwconv_fwd: bad args");
   RD_NS(dtype, launch_dwconv_fwd)(x, w, y, N, H, W, C, OH, OW, k, s, p, RD_DT(dtype), S(stream), nullptr);
   return done("rd_dwconv_fwd");
 }
 int32_t rd_dwconv_stats_rows(int32_t N, int32_t OH, int32_t OW, int32_t C, int32_t k, int32_t s) { return rd::dwconv_stats_rows(N, OH, OW, C, k, s); }
 int rd_dwconv_fwd_stats(const void* x, const float* w, void* y, float* stats, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW,
                         int32_t k, int32_t s, int32_t p, int32_t dtype, void* stream) {
-  if (!x || !w || !y || !stats || !dt_ok(dtype) || rd::dwconv_stats_rows(N, OH, OW, C, k, s) <= 0) return fail("dwconv_fwd_stats: bad args");
+  if (!x || !w || !y || !stats || !dt_ok(dtype) || !dw_geom_ok(N, H, W, C, OH, OW, k, s, p) || rd::dwconv_stats_rows(N, OH, OW, C, k, s) <= 0) return fail("dwconv_fwd_stats: bad args");
   RD_NS(dtype, launch_dwconv_fwd)(x, w, y, N, H, W, C, OH, OW, k, s, p, RD_DT(dtype), S(stream), stats);
   return done("rd_dwconv_fwd_stats");
 }
 int rd_dwconv_dgrad(const void* dy, const float* w, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, int32_t k,
                     int32_t s, int32_t p, int32_t dtype, void* stream) {
-  if (!dy || !w || !dx || !dt_ok(dtype) || k > 5 || k < 1) return fail("dwconv_dgrad: bad args");
+  if (!dy || !w || !dx || !dt_ok(dtype) || !dw_geom_ok(N, H, W, C, OH, OW, k, s, p)) return fail("dwconv_dgrad: bad args");
   RD_NS(dtype, launch_dwconv_dgrad)(dy, w, dx, N, H, W, C, OH, OW, k, s, p, RD_DT(dtype), S(stream));
   return done("rd_dwconv_dgrad");
 }
 int rd_dwconv_wgrad(const void* x, const void* dy, float* partial, float* dw, int32_t accumulate, int32_t N, int32_t H, int32_t W, int32_t C,
                     int32_t OH, int32_t OW, int32_t k, int32_t s, int32_t p, int32_t dtype, void* stream) {
-  if (!x || !dy || !partial || !dw || !dt_ok(dtype) || k > 5 || k < 1) return fail("dwconv_wgrad: bad args");
+  if (!x || !dy || !partial || !dw || !dt_ok(dtype) || !dw_geom_ok(N, H, W, C, OH, OW, k, s, p)) return fail("dwconv_wgrad: bad args");
   RD_NS(dtype, launch_dwconv_wgrad)(x, dy, partial, dw, accumulate, N, H, W, C, OH, OW, k, s, p, RD_DT(dtype), S(stream), nullptr);
   return done("rd_dwconv_wgrad");
 }
@@ -990,7 +996,7 @@ static_assert(sizeof(rd_dw_wgrad_item) == sizeof(rdt::DwWgradItem), "rd_dw_wgrad
 int rd_dwconv_wgrad_partial(const void* x, const void* dy, float* partial, float* dw, int32_t accumulate, int32_t N, int32_t H, int32_t W,
                             int32_t C, int32_t OH, int32_t OW, int32_t k, int32_t s, int32_t p, int32_t dtype, rd_dw_wgrad_item* item,
                             void* stream) {
-  if (!x || !dy || !partial || !dw || !item || !dt_ok(dtype) || k > 5 || k < 1) return fail("dwconv_wgrad_partial: bad args");
+  if (!x || !dy || !partial || !dw || !item || !dt_ok(dtype) || !dw_geom_ok(N, H, W, C, OH, OW, k, s, p)) return fail("dwconv_wgrad_partial: bad args");
   RD_NS(dtype, launch_dwconv_wgrad)(x, dy, partial, dw, accumulate, N, H, W, C, OH, OW, k, s, p, RD_DT(dtype), S(stream),
                                     reinterpret_cast<rdt::DwWgradItem*>(item));
   return done("rd_dwconv_wgrad_partial");
@@ -1010,13 +1016,13 @@ int rd_bn_stats(const void* y, float* partial, int64_t pixels, int32_t C, int32_
 }
 int rd_bilinear_fwd(const void* x, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, int32_t align, int32_t dtype,
                     void* stream) {
-  if (!x || !y || !dt_ok(dtype)) return fail("bilinear_fwd: bad args");
+  if (!x || !y || !dt_ok(dtype) || !sizes_ok(N, H, W, C, OH, OW)) return fail("bilinear_fwd: bad args");
   RD_NS(dtype, launch_bilinear)(x, y, N, H, W, C, OH, OW, align, 0, RD_DT(dtype), S(stream));
   return done("rd_bilinear_fwd");
 }
 int rd_bilinear_bwd(const void* dy, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, int32_t align, int32_t dtype,
                     void* stream) {
-  if (!dy || !dx || !dt_ok(dtype)) return fail("bilinear_bwd: bad args");
+  if (!dy || !dx || !dt_ok(dtype) || !sizes_ok(N, H, W, C, OH, OW)) return fail("bilinear_bwd: bad args");
   RD_NS(dtype, launch_bilinear)(dy, dx, N, H, W, C, OH, OW, align, 1, RD_DT(dtype), S(stream));
   return done("rd_bilinear_bwd");
 }
