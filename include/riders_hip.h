@@ -523,6 +523,37 @@ typedef struct rd_adam_groups {
 } rd_adam_groups;
 int rd_adam_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const rd_adam_groups* groups,
                         float grad_scale, const int32_t* skip_flag, void* stream);
+/* fp16 mode with a DYNAMIC loss scale: torch.amp.GradScaler's semantics with torch.optim.Adam, kept on the device (no step synchronises with
+ * the host, and a captured backward reads the live scale).  The state is 32 bytes of DEVICE memory owned by the caller.  One step is:
+ * the backward seeded with the `scale` word (read by the kernels, not by the host); rd_grad_finite_check(grad, n, &state->found_inf);
+ * every Adam launch through rd_adam_step_groups_scaled; rd_loss_scale_update once. */
+typedef struct rd_loss_scale_state {
+  float scale;             /* the backward's seed reads this word */
+  float inv_scale;         /* (float)(1.0 / (double)scale), as torch's unscale computes it */
+  int32_t found_inf;       /* raised by rd_grad_finite_check(&state->found_inf) for the current step */
+  int32_t skipped;         /* steps skipped so far: (found_inf, skipped) is the int32[2] `flag` of the entries above */
+  int32_t growth_tracker;  /* consecutive finite steps since the scale last changed */
+  int32_t backoffs;        /* scale reductions taken */
+  int32_t growths;         /* scale increases taken */
+  int32_t reserved;
+} rd_loss_scale_state;
+/* Writes every field: scale, its reciprocal, the growth tracker, zero flags and counters.  Refuses a scale that is not finite, not positive
+ * or below FLT_MIN (its reciprocal would not be finite), and a negative tracker. */
+int rd_loss_scale_init(rd_loss_scale_state* state, float scale, int32_t growth_tracker, void* stream);
+/* torch._amp_update_scale_ on one device thread, in the place of rd_adam_skip_count.  found_inf raised: scale *= backoff_factor, the tracker
+ * returns to 0, skipped and backoffs count one.  Otherwise the tracker counts one; when it reaches growth_interval the scale becomes
+ * scale * growth_factor if that is finite (growths counts one) and the tracker returns to 0 either way.  Then inv_scale is recomputed and
+ * found_inf cleared.  ONE departure from torch: a backoff that would take the scale below FLT_MIN is not taken (the step still counts as
+ * skipped; backoffs does not count it) -- torch lets the scale go denormal, 1 / scale overflows to inf and the next unscale poisons the
+ * moments.  Refuses growth_factor <= 1, backoff_factor outside (0, 1) and growth_interval < 1. */
+int rd_loss_scale_update(rd_loss_scale_state* state, float growth_factor, float backoff_factor, int32_t growth_interval, void* stream);
+/* rd_adam_step_groups reading the live state: (1) the launch writes nothing while state->found_inf != 0; (2) the gradient is multiplied by
+ * grad_scale * state->inv_scale; (3) group k's bias corrections use the EFFECTIVE step max(1, groups->step[k] - (state->skipped -
+ * skipped_base)), formed on the device in double precision: the host counts a step before the device decides to skip it, and skipped_base
+ * is the number of skips the host has already taken back out of groups->step.  The group table is validated as for rd_adam_step_groups;
+ * a NULL state is refused. */
+int rd_adam_step_groups_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const rd_adam_groups* groups,
+                               float grad_scale, const rd_loss_scale_state* state, int32_t skipped_base, void* stream);
 
 /* ---- routing options: kernel-selection switches for tests and A/B tools (the product path reads no environment variable).  Names and
  * ranges: kOpts in csrc/rd_api.cpp (e.g. "conv3x3_min_blocks", "frag_v128", "frag32_v128", "wgrad_tr_tw"); values are clamped; an unknown

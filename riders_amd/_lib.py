@@ -110,6 +110,13 @@ class AdamGroups(ctypes.Structure):
                 ("eps", ctypes.c_float * RD_ADAM_MAX_GROUPS), ("weight_decay", ctypes.c_float * RD_ADAM_MAX_GROUPS)]
 
 
+class LossScaleState(ctypes.Structure):
+    """rd_loss_scale_state: the 32 bytes of DEVICE memory of the dynamic loss scale (this mirror describes the layout; the entries take the
+    device address).  (found_inf, skipped) at bytes 8..15 is the int32[2] flag pair rd_grad_finite_check and rd_adam_skip_count know."""
+    _fields_ = [("scale", ctypes.c_float), ("inv_scale", ctypes.c_float), ("found_inf", ctypes.c_int32), ("skipped", ctypes.c_int32),
+                ("growth_tracker", ctypes.c_int32), ("backoffs", ctypes.c_int32), ("growths", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 _SCALARS = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
     "float": ctypes.c_float, "double": ctypes.c_double,

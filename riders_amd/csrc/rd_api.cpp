@@ -5,7 +5,9 @@
 #define rd rd_f16
 #include "rd_kernels_decl.h"
 #undef rd
+#include <float.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -915,12 +917,11 @@ int rd_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n
   rd::launch_adam(p, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), gscale, S(stream), skip_flag);
   return done("rd_adam_step_guarded");
 }
-int rd_adam_step_groups(float* p, const float* g, float* m, float* v, int64_t n, const rd_adam_groups* groups, float gscale,
-                        const int32_t* skip_flag, void* stream) {
-  if (!p || !g || !m || !v || !groups) return fail("adam_groups: null pointer");
+// the group table of both rd_adam_step_groups launches.  d == nullptr: bias corrections formed here (the static launch); otherwise the kernel
+// forms them from d->step and the device's skip count, and step_size carries the bare lr
+static int adam_groups_table(const rd_adam_groups* groups, int64_t n, rd::AdamGroupTable& t, rd::AdamDynTable* d) {
   const int count = groups->count;
   if (count < 1 || count > RD_ADAM_MAX_GROUPS) return fail("adam_groups: count must be 1..%d (got %d)", RD_ADAM_MAX_GROUPS, count);
-  rd::AdamGroupTable t;
   t.inactive_mask = 0;
   int64_t prev = 0;
   for (int k = 0; k < count; k++) {
@@ -936,21 +937,62 @@ int rd_adam_step_groups(float* p, const float* g, float* m, float* v, int64_t n,
     if (live && !inactive && groups->step[k] < 1) return fail("adam_groups: step[%d] must be >= 1", k);
     t.end[k] = live ? groups->end[k] : n;
     if (inactive) t.inactive_mask |= 1 << k;
+    if (d) d->step[k] = 1;
     if (!live || inactive) {
       t.step_size[k] = t.b1[k] = t.b2[k] = t.eps[k] = t.wd[k] = 0.f; t.decay[k] = t.bc2_sqrt[k] = 1.f;
       continue;
     }
     const float lr = groups->lr[k], b1 = groups->beta1[k], b2 = groups->beta2[k], wd = groups->weight_decay[k];
     const bool decoupled = groups->flags[k] & RD_ADAM_DECOUPLED;
-    double bc1 = 1.0 - pow((double)b1, (double)groups->step[k]), bc2 = 1.0 - pow((double)b2, (double)groups->step[k]);
-    t.step_size[k] = lr / (float)bc1;      // rd_adam_step's kernel divides the same two fp32 values
     t.b1[k] = b1; t.b2[k] = b2; t.eps[k] = groups->eps[k];
     t.wd[k] = decoupled ? 0.f : wd;
     t.decay[k] = decoupled ? (float)(1.0 - (double)lr * (double)wd) : 1.f;
+    if (d) {
+      d->step[k] = (int)(groups->step[k] < 0x7fffffff ? groups->step[k] : 0x7fffffff);
+      t.step_size[k] = lr; t.bc2_sqrt[k] = 1.f;
+      continue;
+    }
+    double bc1 = 1.0 - pow((double)b1, (double)groups->step[k]), bc2 = 1.0 - pow((double)b2, (double)groups->step[k]);
+    t.step_size[k] = lr / (float)bc1;      // rd_adam_step's kernel divides the same two fp32 values
     t.bc2_sqrt[k] = (float)sqrt(bc2);
   }
+  return 0;
+}
+int rd_adam_step_groups(float* p, const float* g, float* m, float* v, int64_t n, const rd_adam_groups* groups, float gscale,
+                        const int32_t* skip_flag, void* stream) {
+  if (!p || !g || !m || !v || !groups) return fail("adam_groups: null pointer");
+  rd::AdamGroupTable t;
+  if (int rc = adam_groups_table(groups, n, t, nullptr)) return rc;
   rd::launch_adam_groups(p, g, m, v, n, t, gscale, S(stream), skip_flag);
   return done("rd_adam_step_groups");
+}
+static_assert(sizeof(rd_loss_scale_state) == 32 && sizeof(rd::LossScaleState) == 32, "rd_loss_scale_state is 32 bytes");
+static_assert(offsetof(rd_loss_scale_state, found_inf) == 8 && offsetof(rd_loss_scale_state, skipped) == 12, "(found_inf, skipped) is the flag pair");
+int rd_adam_step_groups_scaled(float* p, const float* g, float* m, float* v, int64_t n, const rd_adam_groups* groups, float gscale,
+                               const rd_loss_scale_state* state, int32_t skipped_base, void* stream) {
+  if (!p || !g || !m || !v || !groups || !state) return fail("adam_groups: null pointer");
+  rd::AdamGroupTable t;
+  rd::AdamDynTable d;
+  if (int rc = adam_groups_table(groups, n, t, &d)) return rc;
+  d.state = reinterpret_cast<const rd::LossScaleState*>(state);
+  d.skipped_base = skipped_base;
+  rd::launch_adam_groups_scaled(p, g, m, v, n, t, d, gscale, S(stream));
+  return done("rd_adam_step_groups_scaled");
+}
+int rd_loss_scale_init(rd_loss_scale_state* state, float scale, int32_t growth_tracker, void* stream) {
+  if (!state) return fail("loss_scale_init: null pointer");
+  if (!(scale >= FLT_MIN && scale <= FLT_MAX)) return fail("loss_scale_init: scale must be finite and >= FLT_MIN (got %g)", (double)scale);
+  if (growth_tracker < 0) return fail("loss_scale_init: growth_tracker must be >= 0");
+  rd::launch_loss_scale_init(reinterpret_cast<rd::LossScaleState*>(state), scale, growth_tracker, S(stream));
+  return done("rd_loss_scale_init");
+}
+int rd_loss_scale_update(rd_loss_scale_state* state, float growth_factor, float backoff_factor, int32_t growth_interval, void* stream) {
+  if (!state) return fail("loss_scale_update: null pointer");
+  if (!(growth_factor > 1.f && growth_factor <= FLT_MAX)) return fail("loss_scale_update: growth_factor must be > 1 (got %g)", (double)growth_factor);
+  if (!(backoff_factor > 0.f && backoff_factor < 1.f)) return fail("loss_scale_update: backoff_factor must be in (0, 1) (got %g)", (double)backoff_factor);
+  if (growth_interval < 1) return fail("loss_scale_update: growth_interval must be >= 1 (got %d)", growth_interval);
+  rd::launch_loss_scale_update(reinterpret_cast<rd::LossScaleState*>(state), growth_factor, backoff_factor, growth_interval, S(stream));
+  return done("rd_loss_scale_update");
 }
 int rd_adam_skip_count(int32_t* flag, void* stream) {
   if (!flag) return fail("adam_skip_count: null pointer");

@@ -211,6 +211,23 @@ struct AdamGroupTable {
 };
 void launch_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, float gscale, hipStream_t st,
                         const int* skip);
+// dynamic loss scale (rd_loss_scale_state of the public header, DEVICE memory): the backward's seed reads `scale`, the scaled Adam launch reads
+// `inv_scale`, `found_inf` and `skipped`, the update kernel is the only writer besides rd_grad_finite_check's atomic on `found_inf`
+struct LossScaleState {
+  float scale, inv_scale;
+  int found_inf, skipped, growth_tracker, backoffs, growths, reserved;
+};
+// rd_adam_step_groups_scaled: the bias corrections are formed ON THE DEVICE from the host step count less the skips counted since
+// `skipped_base`, so the table's step_size holds the bare lr and bc2_sqrt is not read; steps above INT32_MAX are clamped (beta^step is 0 there)
+struct AdamDynTable {
+  const LossScaleState* state;
+  int skipped_base;
+  int step[kAdamMaxGroups];
+};
+void launch_adam_groups_scaled(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, const AdamDynTable& d,
+                               float gscale, hipStream_t st);
+void launch_loss_scale_init(LossScaleState* s, float scale, int growth_tracker, hipStream_t st);
+void launch_loss_scale_update(LossScaleState* s, float growth, float backoff, int interval, hipStream_t st);
 
 
 // rd_dwconv.hip

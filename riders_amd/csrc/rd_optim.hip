@@ -79,10 +79,23 @@ __device__ __forceinline__ int64_t adam_end(const AdamGroupTable& t, int g) {
   return r;
 }
 struct AdamConsts { float step, b1, b2, eps, wd, decay, bc2_sqrt; };
-__device__ __forceinline__ AdamConsts adam_consts(const AdamGroupTable& t, int g) {
+// where a group's two bias-correction constants come from: the table itself (rd_adam_step_groups: formed on the host, selected like every other
+// constant) or the block's LDS (rd_adam_step_groups_scaled: formed on the device, LDS takes a runtime index)
+struct AdamBiasTable {
+  const AdamGroupTable& t;
+  __device__ __forceinline__ float step_size(int g) const { return adam_sel(t.step_size, g); }
+  __device__ __forceinline__ float bc2_sqrt(int g) const { return adam_sel(t.bc2_sqrt, g); }
+};
+struct AdamBiasLds {
+  const float* sm;      // [0, 8): step sizes, [8, 16): sqrt(bias correction 2)
+  __device__ __forceinline__ float step_size(int g) const { return sm[g]; }
+  __device__ __forceinline__ float bc2_sqrt(int g) const { return sm[kAdamMaxGroups + g]; }
+};
+template <class Bias>
+__device__ __forceinline__ AdamConsts adam_consts(const AdamGroupTable& t, const Bias& bias, int g) {
   AdamConsts c;
-  c.step = adam_sel(t.step_size, g); c.b1 = adam_sel(t.b1, g); c.b2 = adam_sel(t.b2, g); c.eps = adam_sel(t.eps, g);
-  c.wd = adam_sel(t.wd, g); c.decay = adam_sel(t.decay, g); c.bc2_sqrt = adam_sel(t.bc2_sqrt, g);
+  c.step = bias.step_size(g); c.b1 = adam_sel(t.b1, g); c.b2 = adam_sel(t.b2, g); c.eps = adam_sel(t.eps, g);
+  c.wd = adam_sel(t.wd, g); c.decay = adam_sel(t.decay, g); c.bc2_sqrt = bias.bc2_sqrt(g);
   return c;
 }
 // adam_kernel's arithmetic with one group's constants; decoupled decay scales p first (decay = 1 and p * 1 = p for a coupled group)
@@ -101,10 +114,11 @@ __device__ __forceinline__ void adam_update4(float* p, const float* g, float* m,
   st4(p + (i4 << 2), pp); st4(m + (i4 << 2), mm); st4(v + (i4 << 2), vv);
 }
 
-__global__ __launch_bounds__(256) void adam_groups_kernel(
-    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
-    float gscale, const int* __restrict__ skip) {
-  if (skip && *skip) return;
+// the one loop of both group kernels (always inlined; Bias is the only thing the two instantiations differ in)
+template <class Bias>
+__device__ __forceinline__ void adam_groups_body(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable& t,
+    const Bias& bias, float gscale) {
   const int64_t n4 = n >> 2;
   // one chunk = the 256 consecutive 16-byte vectors a block handles per grid-stride iteration.  A block's chunks ascend: the outer loop looks the
   // group of a chunk up, the inner loop is adam_kernel's loop over the block's chunks that lie wholly inside that group (one scalar compare each)
@@ -117,7 +131,7 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(
       const int64_t i = c0 + threadIdx.x;
       if (i < n4) {
         const int gi = adam_group_of(t, i << 2);
-        if (!((t.inactive_mask >> gi) & 1)) adam_update4(p, g, m, v, i, adam_consts(t, gi), gscale);
+        if (!((t.inactive_mask >> gi) & 1)) adam_update4(p, g, m, v, i, adam_consts(t, bias, gi), gscale);
       }
       c0 += stride;
       continue;
@@ -129,7 +143,7 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(
       do c0 += stride; while (c0 <= bound);
       continue;
     }
-    const AdamConsts c = adam_consts(t, glo);
+    const AdamConsts c = adam_consts(t, bias, glo);
     do {
       const int64_t i = c0 + threadIdx.x;
       if (i < n4) adam_update4(p, g, m, v, i, c, gscale);
@@ -140,14 +154,86 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(
   const int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) {
     const int gt = adam_group_of(t, n4 << 2);
-    if (!((t.inactive_mask >> gt) & 1)) adam_update(p[i], g[i], m[i], v[i], adam_consts(t, gt), gscale);
+    if (!((t.inactive_mask >> gt) & 1)) adam_update(p[i], g[i], m[i], v[i], adam_consts(t, bias, gt), gscale);
   }
+}
+
+__global__ __launch_bounds__(256) void adam_groups_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
+    float gscale, const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  adam_groups_body(p, g, m, v, n, t, AdamBiasTable{t}, gscale);
+}
+
+// ---- dynamic loss scale (torch.amp.GradScaler's semantics, kept on the device) -------------------------------------------------------------
+// The scaled launch reads the live state: it writes nothing while found_inf is raised, unscales with gscale * inv_scale, and forms every
+// group's bias corrections from the EFFECTIVE step (host step less the skips the host has not yet taken out of its counters), in double as
+// rd_api.cpp does for the static launch.  Per block: thread k < 8 forms group k's pair, LDS (64 bytes) hands it to the others.
+__device__ __forceinline__ int adam_seli(const int (&a)[kAdamMaxGroups], int g) {
+  int r = a[0];
+#pragma unroll
+  for (int k = 1; k < kAdamMaxGroups; k++) r = g == k ? a[k] : r;
+  return r;
+}
+__global__ __launch_bounds__(256) void adam_groups_scaled_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
+    const AdamDynTable d, float gscale) {
+  if (d.state->found_inf) return;      // uniform: every thread of every block reads the same word
+  __shared__ float sm[2 * kAdamMaxGroups];
+  if (threadIdx.x < kAdamMaxGroups) {
+    const int k = threadIdx.x;
+    const int late = d.state->skipped - d.skipped_base;
+    const int hs = adam_seli(d.step, k);
+    const double eff = (double)(hs - late > 1 ? hs - late : 1);
+    const float lr = adam_sel(t.step_size, k);
+    const double bc1 = 1.0 - pow((double)adam_sel(t.b1, k), eff), bc2 = 1.0 - pow((double)adam_sel(t.b2, k), eff);
+    sm[k] = lr / (float)bc1;
+    sm[kAdamMaxGroups + k] = (float)sqrt(bc2);
+  }
+  __syncthreads();
+  adam_groups_body(p, g, m, v, n, t, AdamBiasLds{sm}, gscale * d.state->inv_scale);
+}
+__global__ void loss_scale_init_kernel(LossScaleState* __restrict__ s, float scale, int growth_tracker) {
+  s->scale = scale; s->inv_scale = (float)(1.0 / (double)scale);
+  s->found_inf = 0; s->skipped = 0; s->growth_tracker = growth_tracker; s->backoffs = 0; s->growths = 0; s->reserved = 0;
+}
+// torch._amp_update_scale_ on one thread; the one departure: a backoff that would leave the normal range is not taken (see the header)
+__global__ void loss_scale_update_kernel(LossScaleState* __restrict__ s, float growth, float backoff, int interval) {
+  float scale = s->scale;
+  if (s->found_inf) {
+    const float lower = scale * backoff;
+    if (lower >= 1.17549435e-38f) { scale = lower; s->backoffs += 1; }
+    s->growth_tracker = 0;
+    s->skipped += 1;
+  } else {
+    int tracker = s->growth_tracker + 1;
+    if (tracker == interval) {
+      const float higher = scale * growth;
+      if (fabsf(higher) <= 3.4028234e38f) { scale = higher; s->growths += 1; }
+      tracker = 0;
+    }
+    s->growth_tracker = tracker;
+  }
+  s->scale = scale;
+  s->inv_scale = (float)(1.0 / (double)scale);
+  s->found_inf = 0;
 }
 
 void launch_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, float gscale, hipStream_t st,
                         const int* skip) {
   unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 1024), 2048));
   hipLaunchKernelGGL(adam_groups_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, t, gscale, skip);
+}
+void launch_adam_groups_scaled(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, const AdamDynTable& d,
+                               float gscale, hipStream_t st) {
+  unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 1024), 2048));
+  hipLaunchKernelGGL(adam_groups_scaled_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, t, d, gscale);
+}
+void launch_loss_scale_init(LossScaleState* s, float scale, int growth_tracker, hipStream_t st) {
+  hipLaunchKernelGGL(loss_scale_init_kernel, dim3(1), dim3(1), 0, st, s, scale, growth_tracker);
+}
+void launch_loss_scale_update(LossScaleState* s, float growth, float backoff, int interval, hipStream_t st) {
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(1), 0, st, s, growth, backoff, interval);
 }
 
 void launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,

@@ -152,8 +152,9 @@ def set_defer_wgrad(flag):
 
 def set_compute_dtype(dt):
     """Activation storage dtype of subsequently executed regions: 'fp32', 'bf16' or 'fp16' (accumulation is always fp32).
-    fp16 (BASELINE.json configs[4]) has a narrow exponent: train with a static loss scale (rcnet_main / sml_main `loss_scale`, folded back
-    into Adam's grad_scale) -- the loss is a mean over millions of pixels and its raw gradients underflow fp16."""
+    fp16 (BASELINE.json configs[4]) has a narrow exponent: train with a loss scale (rcnet_main / sml_main `loss_scale`: a float is a static
+    scale folded back into Adam's grad_scale, an optim.DynamicLossScale follows torch.amp.GradScaler on the device) -- the loss is a mean over
+    millions of pixels and its raw gradients underflow fp16."""
     _state["dtype"] = {"fp32": RD_F32, "bf16": RD_BF16, "fp16": RD_F16, RD_F32: RD_F32, RD_BF16: RD_BF16, RD_F16: RD_F16}[dt]
 
 
@@ -809,6 +810,13 @@ class StepTape(object):
         t = self.tape
         if id(loss) not in t.req:
             raise RuntimeError("StepTape.seed: the loss does not depend on any trainable tensor of this tape")
+        if isinstance(value, torch.Tensor):
+            # a device word that changes between replays (optim.DynamicLossScale.scale_tensor): the backward reads THIS tensor, no copy and no
+            # fill -- a fill would be a captured kernel with the value of the capture pass baked in
+            if value.dtype != torch.float32 or value.numel() != 1 or value.device != loss.device:
+                raise ValueError("StepTape.seed: a tensor seed is one float32 element on the loss's device")
+            t.grads[id(loss)] = value.detach().view(1)
+            return
         t.grads[id(loss)] = torch.full((1,), float(value), dtype=torch.float32, device=loss.device)
 
     def backward_stage(self):

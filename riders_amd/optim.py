@@ -31,6 +31,77 @@ _GROUP_DEFAULTS = dict(amsgrad=False, maximize=False, foreach=None, capturable=F
                        decoupled_weight_decay=False)
 
 
+class DynamicLossScale(object):
+    """torch.amp.GradScaler's loss scale for the fp16 mode, kept entirely on the device: 32 bytes (rd_loss_scale_state) that the backward's
+    seed, the finite check, the Adam launches and the update kernel read and write in stream order, so no step synchronises with the host and
+    a captured step (rcnet_main.GraphedStep) reads the scale of the replay, not of the capture.
+
+    Hand it to `loss_scale=` of train_step / compute_gradients / staged_gradients / GraphedStep / GraphedTrainStep (or assign it to
+    `FlatAdam.loss_scale` and seed the backward with `scale_tensor`).  FlatAdam.step() then runs rd_grad_finite_check on the arena, every Adam
+    launch through rd_adam_step_groups_scaled (nothing is written while the flag is up; the gradient is divided by the live scale), and
+    rd_loss_scale_update, which is torch._amp_update_scale_: backoff on a non-finite gradient, growth after `growth_interval` finite steps in
+    a row.  One departure: a backoff that would take the scale below the smallest normal fp32 is not taken.
+
+    Several ranks: the finite check runs in step(), i.e. on the REDUCED arena after the all-reducer's join, and an inf or NaN of one rank
+    survives the sum, so every rank raises the same flag, skips the same step and keeps the same scale without exchanging anything more.
+
+    One scaler serves one optimizer.  get_scale() / skipped_steps() / stats() synchronise; state_dict() / load_state_dict() have GradScaler's
+    layout, so a checkpoint moves between the two."""
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, device=None):
+        if not growth_factor > 1.0:
+            raise ValueError("The growth factor must be > 1.0.")
+        if not 0.0 < backoff_factor < 1.0:
+            raise ValueError("The backoff factor must be in (0, 1).")
+        if int(growth_interval) < 1:
+            raise ValueError("The growth interval must be >= 1.")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._state = torch.zeros(ctypes.sizeof(_lib.LossScaleState) // 4, dtype=torch.int32, device=device)
+        self.scale_tensor = self._state[0:1].view(torch.float32)      # the `scale` word itself: what the backward is seeded with
+        self._flag = self._state[2:4]                                  # (found_inf, skipped): the flag pair of rd_grad_finite_check
+        self._carry = 0      # skips counted before the last load_state_dict (which zeroes the device counters)
+        self._init(init_scale, 0)
+
+    def _init(self, scale, tracker):
+        engine._chk(engine.L().rd_loss_scale_init(engine._p(self._state), ctypes.c_float(scale), int(tracker), engine._stream(self._state)),
+                    "rd_loss_scale_init")
+
+    def update(self):
+        """the step's last launch: found_inf -> backoff and one more skipped step, otherwise the growth tracker; clears found_inf"""
+        engine._chk(engine.L().rd_loss_scale_update(engine._p(self._state), ctypes.c_float(self.growth_factor), ctypes.c_float(self.backoff_factor),
+                                                    self.growth_interval, engine._stream(self._state)), "rd_loss_scale_update")
+
+    def stats(self):
+        """-> dict of the state's fields (synchronises)"""
+        raw = self._state.detach().cpu()
+        f = raw[0:2].view(torch.float32)
+        names = [n for n, _ in _lib.LossScaleState._fields_]
+        out = dict(zip(names, [float(f[0]), float(f[1])] + [int(v) for v in raw[2:]]))
+        out.pop("reserved")
+        return out
+
+    def get_scale(self):
+        return float(self.scale_tensor.item())
+
+    def skipped_steps(self):
+        return self._carry + int(self._state[3].item())
+
+    def state_dict(self):
+        s = self.stats()
+        return dict(scale=s["scale"], growth_factor=self.growth_factor, backoff_factor=self.backoff_factor, growth_interval=self.growth_interval,
+                    _growth_tracker=s["growth_tracker"])
+
+    def load_state_dict(self, sd):
+        if len(sd) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of GradScaler.")
+        self._carry = self.skipped_steps()
+        self.growth_factor, self.backoff_factor = float(sd["growth_factor"]), float(sd["backoff_factor"])
+        self.growth_interval = int(sd["growth_interval"])
+        self._init(float(sd["scale"]), int(sd["_growth_tracker"]))
+
+
 class FlatAdam(object):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False):
         params = [p for p in params]
@@ -93,10 +164,35 @@ class FlatAdam(object):
         self._touched = [False] * len(params)   # slot written by a backward kernel since zero_grad()
         self._ever = [False] * len(params)      # slot has received a gradient at least once (torch: has optimizer state)
         self.grad_scale = 1.0      # 1 / world size, set by parallel.GradientAllReducer (the all-reduce sums)
-        self.loss_scale = 1.0      # static loss scale of the fp16 mode: gradients arrive multiplied by it and are divided here
+        self._loss_scale = 1.0     # loss scale of the fp16 mode: gradients arrive multiplied by it and are divided here (float or DynamicLossScale)
         self._overflow = None      # device int32[2] (flag, skipped steps) of the guarded fp16 step, allocated on first use
         self._skips_reconciled = 0  # skipped steps already taken back out of the host step counters (reconcile_skipped)
+        self._dyn_reconciled = 0    # ... of those the attached DynamicLossScale counted
         engine.set_param_grad_allocator(self._grad_view)
+
+    @property
+    def loss_scale(self):
+        """A float: the static loss scale (1.0: none).  A DynamicLossScale: the scale lives on the device and follows torch.amp.GradScaler; step()
+        then launches rd_grad_finite_check, rd_adam_step_groups_scaled and rd_loss_scale_update and never synchronises.  The host step counters
+        still advance before the device decides to skip, but the scaled launch subtracts the skips not yet reconciled, so every applied update has
+        the bias correction of the number of updates applied.  A parameter that was not written during a skipped step keeps the approximation
+        reconcile_skipped() already has: the skip is taken off its count too."""
+        return self._loss_scale
+
+    @loss_scale.setter
+    def loss_scale(self, value):
+        if isinstance(value, DynamicLossScale):
+            if value is not self._loss_scale:      # attaching synchronises once: skips counted so far belong to whoever counted them
+                self.reconcile_skipped()
+                self._dyn_reconciled = value.skipped_steps()
+            self._loss_scale = value
+            return
+        if isinstance(self._loss_scale, DynamicLossScale):
+            self.reconcile_skipped()
+        self._loss_scale = float(value)
+
+    def _scaler(self):
+        return self._loss_scale if isinstance(self._loss_scale, DynamicLossScale) else None
 
     # kept for callers that read the global step (all parameters that train share it)
     @property
@@ -125,20 +221,30 @@ class FlatAdam(object):
         """fp16 mode: optimizer steps dropped because a scaled gradient was not finite (synchronises).  The host-side step counters (bias
         correction) are advanced before the device decides to skip, so after k skipped steps they run k ahead of the moments until
         `reconcile_skipped()` (called by state_dict()) takes them back -- torch's GradScaler likewise does not advance `step` on a skip."""
+        return self._static_skips() + self._dyn_skips()
+
+    def _static_skips(self):
         return 0 if self._overflow is None else int(self._overflow[1].item())
 
+    def _dyn_skips(self):
+        """skips counted by the attached DynamicLossScale since it was attached (plus those reconciled under an earlier one)"""
+        sc = self._scaler()
+        return self._dyn_reconciled if sc is None else sc.skipped_steps()
+
     def reconcile_skipped(self, warn_after=8):
-        """Subtract the device-side skip count from the host step counters (synchronises; the loss scale is static, so a persistent overflow
-        skips EVERY step: more than `warn_after` skips since the last call raise a warning naming the remedy).  -> skips taken back."""
-        k = self.skipped_steps()
-        new = k - self._skips_reconciled
+        """Subtract the device-side skip count from the host step counters (synchronises; with a static loss scale a persistent overflow
+        skips EVERY step: more than `warn_after` skips since the last call raise a warning naming the remedy.  Under a DynamicLossScale skips
+        are routine -- a few while the scale backs off, then one per growth interval -- and nothing is warned).  -> skips taken back."""
+        ks, kd = self._static_skips(), self._dyn_skips()
+        new_static = ks - self._skips_reconciled
+        new = new_static + kd - self._dyn_reconciled
         if new > 0:
             self.steps = [max(0, s - new) if e else s for s, e in zip(self.steps, self._ever)]
-            self._skips_reconciled = k
-            if new > warn_after:
+            self._skips_reconciled, self._dyn_reconciled = ks, kd
+            if new_static > warn_after and self._scaler() is None:
                 import warnings
                 warnings.warn("FlatAdam: %d optimizer steps were skipped because the scaled fp16 gradient was not finite; lower loss_scale "
-                              "(now %g)" % (new, self.loss_scale))
+                              "(now %g)" % (new_static, self.loss_scale))
         return max(new, 0)
 
     def slot_range(self, params):
@@ -176,6 +282,9 @@ class FlatAdam(object):
 
     def _launch(self, start, end, step):
         g = self.param_groups[0]
+        if self._scaler() is not None:      # one coupled group under a dynamic scale: a table of one through the scaled entry
+            self._launch_groups(start, end, [(g, end, step)])
+            return
         sl = slice(start, end)
         args = (engine._p(self.flat_param[sl]), engine._p(self.flat_grad[sl]), engine._p(self.exp_avg[sl]), engine._p(self.exp_avg_sq[sl]), end - start,
                 ctypes.c_float(g['lr']), ctypes.c_float(g['betas'][0]), ctypes.c_float(g['betas'][1]), ctypes.c_float(g['eps']),
@@ -207,8 +316,16 @@ class FlatAdam(object):
             prev = e
         sl = slice(start, end)
         ptrs = (engine._p(self.flat_param[sl]), engine._p(self.flat_grad[sl]), engine._p(self.exp_avg[sl]), engine._p(self.exp_avg_sq[sl]))
-        skip = engine._p(self._overflow) if self._overflow is not None else None
         st = engine._stream(self.flat_param)
+        sc = self._scaler()
+        if sc is not None:
+            # the host counters run ahead of the moments by the skips not yet reconciled: the kernel takes state->skipped - base off every step
+            base = self._dyn_reconciled - sc._carry
+            rc = engine._tb("optimizer", 28 * live, lambda: engine.L().rd_adam_step_groups_scaled(*ptrs, end - start, t, ctypes.c_float(self.grad_scale),
+                                                                                                  engine._p(sc._state), base, st), "adam")
+            engine._chk(rc, "rd_adam_step_groups_scaled")
+            return
+        skip = engine._p(self._overflow) if self._overflow is not None else None
         rc = engine._tb("optimizer", 28 * live, lambda: engine.L().rd_adam_step_groups(*ptrs, end - start, t, ctypes.c_float(self.grad_scale / self.loss_scale),
                                                                                        skip, st), "adam")
         engine._chk(rc, "rd_adam_step_groups")
@@ -256,7 +373,13 @@ class FlatAdam(object):
         live = [s for s, t in zip(self.steps, self._touched) if t]
         if not live:
             return
-        guarded = self.loss_scale != 1.0     # fp16 mode: a non-finite scaled gradient skips the whole update (device-side, no host sync)
+        scaler = self._scaler()
+        guarded = scaler is None and self.loss_scale != 1.0     # fp16 mode: a non-finite scaled gradient skips the whole update (device-side, no host sync)
+        if scaler is not None:      # the dynamic scale: the flag pair is the scaler's own (found_inf, skipped)
+            if scaler._state.device != self.flat_param.device:
+                raise ValueError("FlatAdam: the DynamicLossScale lives on %s, the arena on %s" % (scaler._state.device, self.flat_param.device))
+            engine._chk(engine.L().rd_grad_finite_check(engine._p(self.flat_grad), self.numel, engine._p(scaler._flag),
+                                                        engine._stream(self.flat_param)), "rd_grad_finite_check")
         if guarded:
             if self._overflow is None:
                 self._overflow = torch.zeros(2, dtype=torch.int32, device=self.flat_param.device)
@@ -284,6 +407,8 @@ class FlatAdam(object):
                     i = j + 1
         if guarded:
             engine._chk(engine.L().rd_adam_skip_count(engine._p(self._overflow), engine._stream(self.flat_param)), "rd_adam_skip_count")
+        if scaler is not None:
+            scaler.update()
         engine.refresh_packed(self._owner)   # one launch re-packs every cached MFMA operand of the rewritten parameters (this optimizer's only)
 
     # ------------------------------------------------------------------ checkpoint interchange with torch.optim.Adam
@@ -317,7 +442,7 @@ class FlatAdam(object):
             self.exp_avg.copy_(sd['exp_avg'])
             self.exp_avg_sq.copy_(sd['exp_avg_sq'])
             self.param_groups[0].update({k: v for k, v in sd['param_groups'][0].items() if k != 'params'})
-            self._skips_reconciled = self.skipped_steps()
+            self._skips_reconciled, self._dyn_reconciled = self._static_skips(), self._dyn_skips()
             return
         groups = sd['param_groups']
         if len(groups) != len(self.param_groups):
@@ -344,7 +469,7 @@ class FlatAdam(object):
                 self.steps[pos] = int(float(st['step']))
                 self._ever[pos] = True
         # the loaded `step` values are updates actually applied: skips counted on the device so far belong to the state that was replaced
-        self._skips_reconciled = self.skipped_steps()
+        self._skips_reconciled, self._dyn_reconciled = self._static_skips(), self._dyn_skips()
         for mine, theirs in zip(self.param_groups, groups):
             hp = {k: v for k, v in theirs.items() if k in _HYPER}
             if 'betas' in hp:

@@ -11,6 +11,7 @@ import torch.distributed
 
 from . import engine
 from .networks import boxes_to_rois
+from .optim import DynamicLossScale
 from .rcnet_model import RCNetModel
 
 # RCNet/train_rcnet_zju.py:28-65
@@ -76,7 +77,13 @@ def prepare_batch(batch):
 
 
 def scaled_backward(loss, optimizer, loss_scale):
-    """loss.backward() with the static loss scale of the fp16 mode (the seed gradient is the scale; Adam divides it out again)."""
+    """loss.backward() with the loss scale of the fp16 mode (the seed gradient is the scale; Adam divides it out again): a float is the static
+    scale, an optim.DynamicLossScale seeds the backward with its device word, which the optimizer's step then adjusts (torch.amp.GradScaler's rule).
+    Several ranks: the step's finite check reads the reduced arena, after the all-reducer's join, so the ranks decide alike."""
+    if isinstance(loss_scale, DynamicLossScale):
+        optimizer.loss_scale = loss_scale
+        loss.backward(loss_scale.scale_tensor.view(loss.shape))
+        return
     optimizer.loss_scale = float(loss_scale)
     if loss_scale == 1.0:
         loss.backward()
@@ -188,10 +195,11 @@ def staged_gradients(fwd_loss, optimizer, on_stage=None, loss_scale=1.0):
     stage mark and calls `on_stage(tag)`, which is where GraphedStep ends one hipGraph capture and begins the next.  The stage hooks
     registered with the engine (the all-reducer's) fire at the same marks."""
     optimizer.zero_grad()
-    optimizer.loss_scale = float(loss_scale)
+    dynamic = isinstance(loss_scale, DynamicLossScale)
+    optimizer.loss_scale = loss_scale if dynamic else float(loss_scale)
     st = engine.StepTape()
     loss = st.forward(fwd_loss)
-    st.seed(loss, loss_scale)
+    st.seed(loss, loss_scale.scale_tensor if dynamic else loss_scale)      # the device word itself: a replay reads the scale of that moment
     while True:
         tag = st.backward_stage()
         if tag is None:

@@ -118,6 +118,7 @@ def forward_loss(model, batch, cfg=ZJU_SML_CONFIG, outlier=None):
 
 
 def compute_gradients(model, optimizer, batch, cfg=ZJU_SML_CONFIG, outlier=None, loss_scale=1.0):
+    """loss_scale (here, in train_step and in GraphedTrainStep): a float (static) or an optim.DynamicLossScale, as rcnet_main.scaled_backward takes it"""
     from .rcnet_main import scaled_backward
     loss = forward_loss(model, batch, cfg, outlier)
     optimizer.zero_grad()
