@@ -118,7 +118,8 @@ int rd_linear_wgrad_batch(const rd_lwg_gemm* gemms, int32_t n_gemm, const rd_lwg
    rstd1, mean2, rstd2); the backward consumes it and writes dx [, dsrc], the LayerNorm parameter gradients, and the output gradients of
    the six linears (dq, dk, dv, dmpre, dhid, dm2pre) whose weight gradients are then one rd_linear_wgrad_batch call:
      Wq: (x, dq)  Wk: (src, dk)  Wv: (src, dv)  Wm: (att, dmpre)  W0: ([x | msg], dhid)  W2: (hid, dm2pre).
-   lnp1 / lnp2 are [N][128][2] fp32 scratch. */
+   lnp1 / lnp2 are [N][128][2] fp32 scratch.  Both calls refuse L or S outside 1..32 and a NULL member they read (the backward reads neither
+   b1 / b2 nor saved.att / saved.msg, which feed the weight gradients only). */
 typedef struct rd_loftr_weights {
   const void *wq, *wk, *wv, *wm, *w0, *w2;
   const float *g1, *b1, *g2, *b2;

@@ -205,6 +205,8 @@ int rd_loftr_layer_bwd(const void* x, const void* src, const rd_loftr_weights* w
   if (!x || !src || !w || !sv || !g) return fail("loftr_layer_bwd: null pointer");
   if (!dt_ok(dtype)) return fail("loftr_layer_bwd: bad dtype %d", dtype);
   if (N < 0 || L <= 0 || S <= 0 || L > 32 || S > 32) return fail("loftr_layer_bwd: needs 1..32 tokens per sequence (L=%d S=%d)", L, S);
+  if (!w->wq || !w->wk || !w->wv || !w->wm || !w->w0 || !w->w2 || !w->g1 || !w->g2) return fail("loftr_layer_bwd: null weight");
+  if (!sv->q || !sv->k || !sv->v || !sv->mpre || !sv->hid || !sv->m2pre || !sv->stats) return fail("loftr_layer_bwd: null saved buffer");
   if (!g->dout || !g->dm2pre || !g->dhid || !g->dmpre || !g->datt || !g->dq || !g->dk || !g->dv || !g->dx || (src != x && !g->dsrc))
     return fail("loftr_layer_bwd: null gradient buffer");
   if (g->dsrc_accumulate && src == x) return fail("loftr_layer_bwd: dsrc_accumulate is for cross attention (src != x)");
