@@ -555,6 +555,44 @@ int rd_loss_scale_update(rd_loss_scale_state* state, float growth_factor, float 
  * a NULL state is refused. */
 int rd_adam_step_groups_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const rd_adam_groups* groups,
                                float grad_scale, const rd_loss_scale_state* state, int32_t skipped_base, void* stream);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) on the device: one read of the gradient arena, one single-block launch, and
+ * an Adam launch that multiplies the gradient by one more scalar -- no host synchronisation and no second write of the gradients.  One step is:
+ * rd_grad_norm_partial over every run of gradients that counts (accumulate = 0 for the first, 1 for the others); rd_grad_clip_finalize once;
+ * every Adam launch through rd_adam_step_groups_clipped.  The state is 32 bytes of DEVICE memory owned by the caller, the partial buffer
+ * RD_GRAD_NORM_ROWS doubles of device memory owned by the caller. */
+#define RD_GRAD_NORM_ROWS 2048
+#define RD_GRAD_NORM_L2 2
+#define RD_GRAD_NORM_INF 0
+typedef struct rd_grad_clip_state {
+  float total_norm;        /* the norm of the last finalize, rounded to fp32 */
+  float coef;              /* min(1, max_norm / (total_norm + 1e-6)): read by rd_adam_step_groups_clipped */
+  int32_t passes;          /* finalize launches so far */
+  int32_t clipped;         /* ... of those with coef < 1 */
+  int32_t nonfinite;       /* ... of those whose norm was inf or NaN */
+  int32_t reserved[3];
+} rd_grad_clip_state;
+/* Writes every field: zero norm and counters, coef = 1 (a clipped launch before any finalize is the unclipped one). */
+int rd_grad_clip_init(rd_grad_clip_state* state, void* stream);
+/* One grid-stride pass over grad[0..n).  Every element is multiplied by pre = grad_scale (state NULL) or grad_scale * state->inv_scale (read
+ * live) BEFORE it is squared (norm_kind RD_GRAD_NORM_L2) or its absolute value enters the maximum (RD_GRAD_NORM_INF; a NaN stays, as in torch):
+ * torch's order, unscale then norm.  Accumulation is fp32 per thread and wave, double from there on; block b leaves one double in partial[b]
+ * and no floating-point atomic is used, so a repeated call returns the same bits.  accumulate = 0: every one of the `rows` rows is defined
+ * afterwards (rows without data hold 0); accumulate = 1: each block adds to (takes the maximum with) its own row, for a norm over several
+ * ranges -- launches on one stream are ordered.  finite_flag (may be NULL): raised exactly as rd_grad_finite_check raises it, from the raw
+ * elements of the same read.  Refuses a NULL grad or partial, n <= 0, an unknown norm kind, rows != RD_GRAD_NORM_ROWS, accumulate not 0 / 1. */
+int rd_grad_norm_partial(const float* grad, int64_t n, float grad_scale, const rd_loss_scale_state* state, int32_t norm_kind, double* partial,
+                         int32_t rows, int32_t accumulate, int32_t* finite_flag, void* stream);
+/* One block: the rows summed in a fixed order in double (RD_GRAD_NORM_INF: their maximum), the square root, the result rounded to fp32, and
+ * coef = min(1, max_norm / (total_norm + 1e-6f)) in fp32 as torch.nn.utils.clip_grad._clip_grads_with_norm_ forms it: a NaN norm gives a NaN
+ * coefficient (torch.clamp lets it through), an infinite norm gives 0.  Counts the pass, whether it clipped and whether the norm was finite.
+ * Refuses a NULL pointer, an unknown norm kind, rows != RD_GRAD_NORM_ROWS and a max_norm that is not a finite positive number. */
+int rd_grad_clip_finalize(const double* partial, int32_t rows, float max_norm, int32_t norm_kind, rd_grad_clip_state* state, void* stream);
+/* rd_adam_step_groups (state NULL; skip_flag may be NULL) or rd_adam_step_groups_scaled (state given; skip_flag must be NULL) with the gradient
+ * multiplied by (grad_scale [* state->inv_scale]) * clip->coef, in that order: a coefficient of exactly 1 leaves every bit of the unclipped
+ * launch's result.  Refuses a NULL required pointer, n <= 0, both skip_flag and state, and every table rd_adam_step_groups refuses. */
+int rd_adam_step_groups_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const rd_adam_groups* groups,
+                                float grad_scale, const int32_t* skip_flag, const rd_loss_scale_state* state, int32_t skipped_base,
+                                const rd_grad_clip_state* clip, void* stream);
 
 /* ---- routing options: kernel-selection switches for tests and A/B tools (the product path reads no environment variable).  Names and
  * ranges: kOpts in csrc/rd_api.cpp (e.g. "conv3x3_min_blocks", "frag_v128", "frag32_v128", "wgrad_tr_tw"); values are clamped; an unknown

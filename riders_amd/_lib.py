@@ -117,6 +117,17 @@ class LossScaleState(ctypes.Structure):
                 ("growth_tracker", ctypes.c_int32), ("backoffs", ctypes.c_int32), ("growths", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+RD_GRAD_NORM_ROWS = 2048
+GRAD_NORM_L2, GRAD_NORM_INF = 2, 0
+
+
+class GradClipState(ctypes.Structure):
+    """rd_grad_clip_state: the 32 bytes of DEVICE memory of the global-norm gradient clipping (this mirror describes the layout; the entries take
+    the device address).  rd_grad_clip_finalize is the only writer; rd_adam_step_groups_clipped reads `coef`."""
+    _fields_ = [("total_norm", ctypes.c_float), ("coef", ctypes.c_float), ("passes", ctypes.c_int32), ("clipped", ctypes.c_int32),
+                ("nonfinite", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
 _SCALARS = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
     "float": ctypes.c_float, "double": ctypes.c_double,

@@ -1001,6 +1001,48 @@ int rd_adam_skip_count(int32_t* flag, void* stream) {
   rd::launch_adam_skip_count(flag, S(stream));
   return done("rd_adam_skip_count");
 }
+static_assert(sizeof(rd_grad_clip_state) == 32 && sizeof(rd::GradClipState) == 32, "rd_grad_clip_state is 32 bytes");
+static_assert(offsetof(rd_grad_clip_state, coef) == 4 && offsetof(rd::GradClipState, coef) == 4, "coef is the second word");
+static_assert(RD_GRAD_NORM_ROWS == rd::kGradNormRows, "the partial buffer's rows");
+static bool norm_kind_ok(int32_t kind) { return kind == RD_GRAD_NORM_L2 || kind == RD_GRAD_NORM_INF; }
+int rd_grad_clip_init(rd_grad_clip_state* state, void* stream) {
+  if (!state) return fail("grad_clip_init: null pointer");
+  rd::launch_grad_clip_init(reinterpret_cast<rd::GradClipState*>(state), S(stream));
+  return done("rd_grad_clip_init");
+}
+int rd_grad_norm_partial(const float* g, int64_t n, float gscale, const rd_loss_scale_state* state, int32_t norm_kind, double* partial, int32_t rows,
+                         int32_t accumulate, int32_t* finite_flag, void* stream) {
+  if (!g || !partial) return fail("grad_norm_partial: null pointer");
+  if (n <= 0) return fail("grad_norm_partial: n must be > 0 (got %lld)", (long long)n);
+  if (!norm_kind_ok(norm_kind)) return fail("grad_norm_partial: unknown norm kind %d", norm_kind);
+  if (rows != RD_GRAD_NORM_ROWS) return fail("grad_norm_partial: rows must be %d (got %d)", RD_GRAD_NORM_ROWS, rows);
+  if (accumulate != 0 && accumulate != 1) return fail("grad_norm_partial: accumulate must be 0 or 1 (got %d)", accumulate);
+  rd::launch_grad_norm(g, n, gscale, reinterpret_cast<const rd::LossScaleState*>(state), norm_kind == RD_GRAD_NORM_INF, partial, rows, accumulate,
+                       finite_flag, S(stream));
+  return done("rd_grad_norm_partial");
+}
+int rd_grad_clip_finalize(const double* partial, int32_t rows, float max_norm, int32_t norm_kind, rd_grad_clip_state* state, void* stream) {
+  if (!partial || !state) return fail("grad_clip_finalize: null pointer");
+  if (!norm_kind_ok(norm_kind)) return fail("grad_clip_finalize: unknown norm kind %d", norm_kind);
+  if (rows != RD_GRAD_NORM_ROWS) return fail("grad_clip_finalize: rows must be %d (got %d)", RD_GRAD_NORM_ROWS, rows);
+  if (!(max_norm > 0.f && max_norm <= FLT_MAX)) return fail("grad_clip_finalize: max_norm must be finite and > 0 (got %g)", (double)max_norm);
+  rd::launch_grad_clip_finalize(partial, rows, max_norm, norm_kind == RD_GRAD_NORM_INF, reinterpret_cast<rd::GradClipState*>(state), S(stream));
+  return done("rd_grad_clip_finalize");
+}
+int rd_adam_step_groups_clipped(float* p, const float* g, float* m, float* v, int64_t n, const rd_adam_groups* groups, float gscale,
+                                const int32_t* skip_flag, const rd_loss_scale_state* state, int32_t skipped_base, const rd_grad_clip_state* clip,
+                                void* stream) {
+  if (!p || !g || !m || !v || !groups || !clip) return fail("adam_groups_clipped: null pointer");
+  if (n <= 0) return fail("adam_groups_clipped: n must be > 0 (got %lld)", (long long)n);
+  if (skip_flag && state) return fail("adam_groups_clipped: skip_flag and state are exclusive");
+  rd::AdamGroupTable t;
+  rd::AdamDynTable d;
+  if (int rc = adam_groups_table(groups, n, t, state ? &d : nullptr)) return rc;
+  d.state = reinterpret_cast<const rd::LossScaleState*>(state);
+  d.skipped_base = skipped_base;
+  rd::launch_adam_groups_clipped(p, g, m, v, n, t, state ? &d : nullptr, gscale, skip_flag, reinterpret_cast<const rd::GradClipState*>(clip), S(stream));
+  return done("rd_adam_step_groups_clipped");
+}
 
 
 // ---- Scale Map Learner ------------------------------------------------------------------------------------------------

@@ -228,6 +228,20 @@ void launch_adam_groups_scaled(float* p, const float* g, float* m, float* v, int
                                float gscale, hipStream_t st);
 void launch_loss_scale_init(LossScaleState* s, float scale, int growth_tracker, hipStream_t st);
 void launch_loss_scale_update(LossScaleState* s, float growth, float backoff, int interval, hipStream_t st);
+// global-norm gradient clipping (rd_grad_clip_state of the public header, DEVICE memory): the finalize launch is the only writer, the clipped
+// Adam launches read `coef`
+struct GradClipState {
+  float total_norm, coef;
+  int passes, clipped, nonfinite, reserved[3];
+};
+constexpr int kGradNormRows = 2048;      // rows of the partial buffer = the largest grid of the norm pass
+void launch_grad_norm(const float* g, int64_t n, float gscale, const LossScaleState* state, int inf_norm, double* partial, int rows, int accumulate,
+                      int* flag, hipStream_t st);
+void launch_grad_clip_finalize(const double* partial, int rows, float max_norm, int inf_norm, GradClipState* s, hipStream_t st);
+void launch_grad_clip_init(GradClipState* s, hipStream_t st);
+// d == nullptr: bias corrections from the table, optional skip flag; otherwise formed on the device from the live loss-scale state (skip unused)
+void launch_adam_groups_clipped(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, const AdamDynTable* d, float gscale,
+                                const int* skip, const GradClipState* clip, hipStream_t st);
 
 
 // rd_dwconv.hip

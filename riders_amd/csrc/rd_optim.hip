@@ -175,11 +175,8 @@ __device__ __forceinline__ int adam_seli(const int (&a)[kAdamMaxGroups], int g) 
   for (int k = 1; k < kAdamMaxGroups; k++) r = g == k ? a[k] : r;
   return r;
 }
-__global__ __launch_bounds__(256) void adam_groups_scaled_kernel(
-    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
-    const AdamDynTable d, float gscale) {
-  if (d.state->found_inf) return;      // uniform: every thread of every block reads the same word
-  __shared__ float sm[2 * kAdamMaxGroups];
+// every group's bias-correction pair from the effective step, into the block's LDS (both live-state kernels; ends with the block barrier)
+__device__ __forceinline__ void adam_dyn_bias(const AdamGroupTable& t, const AdamDynTable& d, float* sm) {
   if (threadIdx.x < kAdamMaxGroups) {
     const int k = threadIdx.x;
     const int late = d.state->skipped - d.skipped_base;
@@ -191,6 +188,13 @@ __global__ __launch_bounds__(256) void adam_groups_scaled_kernel(
     sm[kAdamMaxGroups + k] = (float)sqrt(bc2);
   }
   __syncthreads();
+}
+__global__ __launch_bounds__(256) void adam_groups_scaled_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
+    const AdamDynTable d, float gscale) {
+  if (d.state->found_inf) return;      // uniform: every thread of every block reads the same word
+  __shared__ float sm[2 * kAdamMaxGroups];
+  adam_dyn_bias(t, d, sm);
   adam_groups_body(p, g, m, v, n, t, AdamBiasLds{sm}, gscale * d.state->inv_scale);
 }
 __global__ void loss_scale_init_kernel(LossScaleState* __restrict__ s, float scale, int growth_tracker) {
@@ -217,6 +221,123 @@ __global__ void loss_scale_update_kernel(LossScaleState* __restrict__ s, float g
   s->scale = scale;
   s->inv_scale = (float)(1.0 / (double)scale);
   s->found_inf = 0;
+}
+
+// ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, kept on the device) ----------------------------------------------------
+// One read of the arena, one tiny launch, then the Adam launch multiplies by one more scalar.  The norm pass multiplies every element by
+// `pre` first (grad_scale, times the live 1 / loss scale when a state is given): torch's order -- unscale, then norm -- and the squares of scaled
+// fp16 gradients cannot overflow where the unscaled ones would not.  Each block leaves ONE double in its own row of the caller's partial
+// buffer (no floating-point atomics: the same bits on every run); accumulate = 1 adds to the row instead, so several launches on one stream
+// -- the runs of slots written since zero_grad() -- build one norm.  The flag, when given, is raised as grad_finite_kernel raises it.
+// a maximum that keeps a NaN once it has seen one, as torch's amax does (fmaxf would drop it)
+template <class T>
+__device__ __forceinline__ T nan_max(T a, T b) { return (b > a || b != b) ? b : a; }
+template <bool INF>
+__device__ __forceinline__ void norm_acc(float& acc, float x) {
+  if (INF) acc = nan_max(acc, fabsf(x)); else acc += x * x;
+}
+template <bool INF>
+__global__ __launch_bounds__(256) void grad_norm_kernel(const float* __restrict__ g, int64_t n, float gscale, const LossScaleState* __restrict__ state,
+                                                        double* __restrict__ partial, int rows, int accumulate, int* __restrict__ flag) {
+  const float pre = state ? gscale * state->inv_scale : gscale;      // the product the scaled Adam launch forms
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float acc = 0.f;
+  bool bad = false;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float gg[4];
+    ld4(g + (i << 2), gg);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      bad |= !(fabsf(gg[e]) <= 3.4028234e38f);
+      norm_acc<INF>(acc, gg[e] * pre);
+    }
+  }
+  for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float x = g[i];
+    bad |= !(fabsf(x) <= 3.4028234e38f);
+    norm_acc<INF>(acc, x * pre);
+  }
+  if (flag && __ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(flag, 1);
+  // wave (xor butterfly: every lane ends with the same value), then the block's four waves in a fixed order, in double
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float other = __shfl_xor(acc, o);
+    acc = INF ? nan_max(acc, other) : acc + other;
+  }
+  __shared__ float sm[4];
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = (double)sm[0];
+#pragma unroll
+    for (int w = 1; w < 4; w++) r = INF ? nan_max(r, (double)sm[w]) : r + (double)sm[w];
+    double* row = partial + blockIdx.x;
+    if (accumulate) r = INF ? nan_max(*row, r) : *row + r;
+    *row = r;
+    if (!accumulate)      // rows no block owns hold 0: the finalize reads every row
+      for (int k = blockIdx.x + gridDim.x; k < rows; k += gridDim.x) partial[k] = 0.0;
+  }
+}
+// one block: the rows in a fixed order in double (thread t takes rows t, t + 256, ..., then a binary tree over the 256 threads), the norm
+// rounded to fp32, and torch's coefficient formed in fp32: min(1, max_norm / (total_norm + 1e-6)); NaN stays NaN, an infinite norm gives 0
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ partial, int rows, float max_norm, int inf_norm,
+                                                                 GradClipState* __restrict__ s) {
+  __shared__ double sm[256];
+  double r = 0.0;
+  for (int k = threadIdx.x; k < rows; k += 256) r = inf_norm ? nan_max(r, partial[k]) : r + partial[k];
+  sm[threadIdx.x] = r;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) sm[threadIdx.x] = inf_norm ? nan_max(sm[threadIdx.x], sm[threadIdx.x + h]) : sm[threadIdx.x] + sm[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float total = (float)(inf_norm ? sm[0] : sqrt(sm[0]));
+    float coef = max_norm / (total + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;      // torch.clamp(max = 1): a NaN passes through
+    s->total_norm = total; s->coef = coef;
+    s->passes += 1;
+    s->clipped += coef < 1.f ? 1 : 0;
+    s->nonfinite += fabsf(total) <= 3.4028234e38f ? 0 : 1;
+  }
+}
+__global__ void grad_clip_init_kernel(GradClipState* __restrict__ s) {
+  s->total_norm = 0.f; s->coef = 1.f; s->passes = 0; s->clipped = 0; s->nonfinite = 0; s->reserved[0] = s->reserved[1] = s->reserved[2] = 0;
+}
+// the two group kernels with the gradient multiplied by (grad_scale [* inv_scale]) * coef: a coefficient of exactly 1 leaves every bit
+__global__ __launch_bounds__(256) void adam_groups_clipped_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
+    float gscale, const int* __restrict__ skip, const GradClipState* __restrict__ clip) {
+  const float coef = clip->coef;
+  if (skip && *skip) return;
+  adam_groups_body(p, g, m, v, n, t, AdamBiasTable{t}, gscale * coef);
+}
+__global__ __launch_bounds__(256) void adam_groups_scaled_clipped_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, const AdamGroupTable t,
+    const AdamDynTable d, float gscale, const GradClipState* __restrict__ clip) {
+  const float coef = clip->coef;      // issued with the state's words, ahead of the dependent prologue
+  if (d.state->found_inf) return;
+  __shared__ float sm[2 * kAdamMaxGroups];
+  adam_dyn_bias(t, d, sm);
+  adam_groups_body(p, g, m, v, n, t, AdamBiasLds{sm}, gscale * d.state->inv_scale * coef);
+}
+
+void launch_grad_norm(const float* g, int64_t n, float gscale, const LossScaleState* state, int inf_norm, double* partial, int rows, int accumulate,
+                      int* flag, hipStream_t st) {
+  unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 1024), rows));
+  if (inf_norm) hipLaunchKernelGGL(grad_norm_kernel<true>, dim3(grid), dim3(256), 0, st, g, n, gscale, state, partial, rows, accumulate, flag);
+  else hipLaunchKernelGGL(grad_norm_kernel<false>, dim3(grid), dim3(256), 0, st, g, n, gscale, state, partial, rows, accumulate, flag);
+}
+void launch_grad_clip_finalize(const double* partial, int rows, float max_norm, int inf_norm, GradClipState* s, hipStream_t st) {
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, st, partial, rows, max_norm, inf_norm, s);
+}
+void launch_grad_clip_init(GradClipState* s, hipStream_t st) { hipLaunchKernelGGL(grad_clip_init_kernel, dim3(1), dim3(1), 0, st, s); }
+void launch_adam_groups_clipped(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, const AdamDynTable* d, float gscale,
+                                const int* skip, const GradClipState* clip, hipStream_t st) {
+  unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 1024), 2048));
+  if (d) hipLaunchKernelGGL(adam_groups_scaled_clipped_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, t, *d, gscale, clip);
+  else hipLaunchKernelGGL(adam_groups_clipped_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, t, gscale, skip, clip);
 }
 
 void launch_adam_groups(float* p, const float* g, float* m, float* v, int64_t n, const AdamGroupTable& t, float gscale, hipStream_t st,

@@ -19,10 +19,17 @@ Parameter groups.  The reference's three training loops pass a list of group dic
 `weight_decay` and torch 2.10's `decoupled_weight_decay` (what AdamW is) are accepted.  The arena is laid out group after group, so a group is
 one contiguous range and rd_adam_step_groups updates all of them in one launch (the group table travels in the kernel arguments).  One group
 with coupled decay -- every optimizer built the flat way -- launches rd_adam_step exactly as before.
+
+Gradient clipping by global norm.  `FlatAdam.set_grad_clip(max_norm, norm_type)` (persistent) and `clip_grad_norm_` below (torch's signature, for
+the unchanged caller) form torch.nn.utils.clip_grad_norm_'s norm and coefficient on the device from one read of the arena and apply the
+coefficient inside the Adam launch (rd_grad_norm_partial, rd_grad_clip_finalize, rd_adam_step_groups_clipped): the gradients are not rewritten
+and nothing waits for the host.  Off -- the default -- step() launches exactly what it launched before.
 """
 import ctypes
 
 import torch
+from torch.nn.utils.clip_grad import clip_grad_norm_ as _torch_clip_grad_norm_      # torch's own, bound once: the fallback of clip_grad_norm_ below,
+#                                                                                   whatever torch.nn.utils.clip_grad_norm_ is aliased to later
 
 from . import _lib, engine
 
@@ -168,6 +175,12 @@ class FlatAdam(object):
         self._overflow = None      # device int32[2] (flag, skipped steps) of the guarded fp16 step, allocated on first use
         self._skips_reconciled = 0  # skipped steps already taken back out of the host step counters (reconcile_skipped)
         self._dyn_reconciled = 0    # ... of those the attached DynamicLossScale counted
+        self._clip = None           # (max_norm, norm kind) of set_grad_clip; None: no clipping, step() launches what it always launched
+        self._clip_armed = False    # clip_grad_norm_ formed the coefficient already: the next step() uses it and runs no norm pass
+        self._clipping = False      # inside step(): this step's Adam launches go through the clipped entry
+        self._clip_state = None     # device int32[8]: rd_grad_clip_state, allocated with the partial rows on first use
+        self._clip_partial = None
+        self._reducer_attached = False
         engine.set_param_grad_allocator(self._grad_view)
 
     @property
@@ -263,6 +276,7 @@ class FlatAdam(object):
         for p in self.params:
             p.grad = None
         self._touched = [False] * len(self.params)
+        self._clip_armed = False      # a coefficient formed by clip_grad_norm_ belongs to the gradients it was formed from
 
     def _gather_foreign_grads(self):
         # gradients produced outside the arena (user-assigned tensors): copy in with a HIP kernel
@@ -280,9 +294,90 @@ class FlatAdam(object):
     def add_param_group(self, param_group):
         raise NotImplementedError("FlatAdam: the arena is sized at construction; pass every parameter group to the constructor")
 
+    # ------------------------------------------------------------------ global-norm gradient clipping
+    def set_grad_clip(self, max_norm, norm_type=2.0):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type) as part of every step(), on the device: one norm pass over the slots
+        written since zero_grad() (rd_grad_norm_partial), one single-block launch that forms torch's coefficient min(1, max_norm / (norm + 1e-6))
+        (rd_grad_clip_finalize), and every Adam launch of the step through rd_adam_step_groups_clipped, which multiplies the gradient by it.
+        Nothing synchronises and the gradients are not rewritten, so train_step, GraphedStep and GraphedTrainStep use it unchanged.  None turns
+        clipping off (the default): step() then launches exactly what it launched before.  norm_type is 2 or inf.
+
+        The norm is taken of the gradient Adam sees: multiplied by grad_scale (1 / world under a GradientAllReducer, on the reduced arena) and
+        divided by the loss scale -- what `scaler.unscale_(opt); clip_grad_norm_(...)` gives.  Under a DynamicLossScale (or a static scale) the
+        norm pass raises the finite flag from the same read and rd_grad_finite_check is not launched.  A non-finite norm: without a loss scale the
+        NaN coefficient reaches the parameters, as torch's error_if_nonfinite=False lets it; with one the step is skipped as it always is."""
+        if max_norm is None:
+            self._clip = None
+            return
+        kind = _norm_kind(norm_type)
+        if kind is None:
+            raise ValueError("FlatAdam.set_grad_clip: norm_type must be 2 or inf (got %r)" % (norm_type,))
+        max_norm = float(max_norm)
+        if not 0.0 < max_norm < float("inf"):
+            raise ValueError("FlatAdam.set_grad_clip: max_norm must be a finite positive number (got %r)" % (max_norm,))
+        self._clip = (max_norm, kind)
+        self._clip_buffers()
+
+    def _clip_buffers(self):
+        if self._clip_state is None:
+            dev = self.flat_param.device
+            self._clip_state = torch.zeros(ctypes.sizeof(_lib.GradClipState) // 4, dtype=torch.int32, device=dev)
+            self._clip_partial = torch.zeros(_lib.RD_GRAD_NORM_ROWS, dtype=torch.float64, device=dev)
+            engine._chk(engine.L().rd_grad_clip_init(engine._p(self._clip_state), engine._stream(self.flat_param)), "rd_grad_clip_init")
+        return self._clip_state
+
+    @property
+    def grad_norm(self):
+        """0-dim fp32 device tensor: the total norm of the last clipped step (a view of the device state: reading it enqueues, it does not wait)"""
+        return self._clip_buffers()[0:1].view(torch.float32)[0]
+
+    def clip_stats(self):
+        """-> dict(total_norm, coef, passes, clipped, nonfinite) of the clipping state (synchronises)"""
+        raw = self._clip_buffers().detach().cpu()
+        f = raw[0:2].view(torch.float32)
+        return dict(total_norm=float(f[0]), coef=float(f[1]), passes=int(raw[2]), clipped=int(raw[3]), nonfinite=int(raw[4]))
+
+    def _touched_runs(self):
+        """[(start, end)] arena element ranges of consecutive slots written since zero_grad()"""
+        runs, n, i = [], len(self.params), 0
+        while i < n:
+            if not self._touched[i]:
+                i += 1
+                continue
+            j = i
+            while j + 1 < n and self._touched[j + 1]:
+                j += 1
+            runs.append((self.offsets[i], self.offsets[j + 1] if j + 1 < n else self.numel))
+            i = j + 1
+        return runs
+
+    def _clip_pass(self, max_norm, kind, flag):
+        """the norm of the written slots (stale slots do not count) and the coefficient, into the device state"""
+        self._clip_buffers()
+        st = engine._stream(self.flat_param)
+        sc = self._scaler()
+        pre = self.grad_scale if sc is not None else self.grad_scale / self.loss_scale
+        state = engine._p(sc._state) if sc is not None else None
+        for k, (a, b) in enumerate(self._touched_runs()):
+            rc = engine._tb("optimizer", 4 * (b - a), lambda: engine.L().rd_grad_norm_partial(
+                engine._p(self.flat_grad[a:b]), b - a, ctypes.c_float(pre), state, kind, engine._p(self._clip_partial), _lib.RD_GRAD_NORM_ROWS,
+                1 if k else 0, flag, st), "grad_norm")
+            engine._chk(rc, "rd_grad_norm_partial")
+        engine._chk(engine.L().rd_grad_clip_finalize(engine._p(self._clip_partial), _lib.RD_GRAD_NORM_ROWS, ctypes.c_float(max_norm), kind,
+                                                     engine._p(self._clip_state), st), "rd_grad_clip_finalize")
+
+    def _clip_now(self, max_norm, kind):
+        """riders_amd.clip_grad_norm_'s fast path: the norm pass and the finalize at once; the next step() multiplies by the coefficient"""
+        self._gather_foreign_grads()
+        if not any(self._touched):
+            return None
+        self._clip_pass(max_norm, kind, None)
+        self._clip_armed = True
+        return self.grad_norm
+
     def _launch(self, start, end, step):
         g = self.param_groups[0]
-        if self._scaler() is not None:      # one coupled group under a dynamic scale: a table of one through the scaled entry
+        if self._scaler() is not None or self._clipping:      # one coupled group under a dynamic scale or clipped: a table of one
             self._launch_groups(start, end, [(g, end, step)])
             return
         sl = slice(start, end)
@@ -318,6 +413,14 @@ class FlatAdam(object):
         ptrs = (engine._p(self.flat_param[sl]), engine._p(self.flat_grad[sl]), engine._p(self.exp_avg[sl]), engine._p(self.exp_avg_sq[sl]))
         st = engine._stream(self.flat_param)
         sc = self._scaler()
+        if self._clipping:
+            skip = engine._p(self._overflow) if (sc is None and self._overflow is not None) else None
+            gscale = self.grad_scale if sc is not None else self.grad_scale / self.loss_scale
+            rc = engine._tb("optimizer", 28 * live, lambda: engine.L().rd_adam_step_groups_clipped(
+                *ptrs, end - start, t, ctypes.c_float(gscale), skip, engine._p(sc._state) if sc is not None else None,
+                self._dyn_reconciled - sc._carry if sc is not None else 0, engine._p(self._clip_state), st), "adam")
+            engine._chk(rc, "rd_adam_step_groups_clipped")
+            return
         if sc is not None:
             # the host counters run ahead of the moments by the skips not yet reconciled: the kernel takes state->skipped - base off every step
             base = self._dyn_reconciled - sc._carry
@@ -372,18 +475,27 @@ class FlatAdam(object):
                 self._ever[i] = True
         live = [s for s, t in zip(self.steps, self._touched) if t]
         if not live:
+            self._clip_armed = False
             return
+        try:
+            self._clipping = self._clip is not None or self._clip_armed
+            self._step_launches(n, live)
+        finally:
+            self._clipping = self._clip_armed = False
+
+    def _step_launches(self, n, live):
         scaler = self._scaler()
         guarded = scaler is None and self.loss_scale != 1.0     # fp16 mode: a non-finite scaled gradient skips the whole update (device-side, no host sync)
         if scaler is not None:      # the dynamic scale: the flag pair is the scaler's own (found_inf, skipped)
             if scaler._state.device != self.flat_param.device:
                 raise ValueError("FlatAdam: the DynamicLossScale lives on %s, the arena on %s" % (scaler._state.device, self.flat_param.device))
-            engine._chk(engine.L().rd_grad_finite_check(engine._p(self.flat_grad), self.numel, engine._p(scaler._flag),
-                                                        engine._stream(self.flat_param)), "rd_grad_finite_check")
-        if guarded:
-            if self._overflow is None:
-                self._overflow = torch.zeros(2, dtype=torch.int32, device=self.flat_param.device)
-            engine._chk(engine.L().rd_grad_finite_check(engine._p(self.flat_grad), self.numel, engine._p(self._overflow),
+        if guarded and self._overflow is None:
+            self._overflow = torch.zeros(2, dtype=torch.int32, device=self.flat_param.device)
+        flag = scaler._flag if scaler is not None else self._overflow if guarded else None
+        if self._clip is not None and not self._clip_armed:      # the norm pass raises the flag from the same read: no finite check of its own
+            self._clip_pass(self._clip[0], self._clip[1], engine._p(flag) if flag is not None else None)
+        elif flag is not None:
+            engine._chk(engine.L().rd_grad_finite_check(engine._p(self.flat_grad), self.numel, engine._p(flag),
                                                         engine._stream(self.flat_param)), "rd_grad_finite_check")
         if len(self.param_groups) > 1 or self.param_groups[0]['decoupled_weight_decay']:
             self._step_groups()
@@ -475,6 +587,57 @@ class FlatAdam(object):
             if 'betas' in hp:
                 hp['betas'] = tuple(hp['betas'])
             mine.update(hp)
+
+
+def _norm_kind(norm_type):
+    """-> the C ABI's norm kind for 2 and inf, None for anything else"""
+    try:
+        v = float(norm_type)
+    except (TypeError, ValueError):
+        return None
+    return _lib.GRAD_NORM_L2 if v == 2.0 else _lib.GRAD_NORM_INF if v == float("inf") else None
+
+
+def _flat_owner(params):
+    """the one live FlatAdam whose parameters with gradients are exactly `params` with gradients, or None"""
+    for ref in reversed(engine._grad_allocs):
+        fn = ref()
+        opt = getattr(fn, "__self__", None)
+        if not isinstance(opt, FlatAdam):
+            continue
+        has = lambda p: p.grad is not None or opt._touched[opt._index[id(p)]]      # noqa: E731
+        if any(id(p) not in opt._index for p in params if p.grad is not None):
+            continue
+        given = set(id(p) for p in params if id(p) in opt._index and has(p))
+        if given and given == set(id(p) for p in opt.params if has(p)):
+            return opt
+    return None
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ for the unchanged caller (`loss.backward(); clip_grad_norm_(model.parameters(), 1.0); optimizer.step()`).
+
+    When `parameters` are exactly the parameters with gradients of one live FlatAdam, error_if_nonfinite is false, norm_type is 2 or inf and no
+    GradientAllReducer is attached to that optimizer, nothing is rewritten: the norm pass and the finalize run at once on the arena (gradients
+    assigned outside it are gathered first; a loss scale attached to the optimizer is divided out, as after `scaler.unscale_`), the optimizer's
+    next step() multiplies the gradient by the coefficient inside its Adam launch, and the device tensor FlatAdam.grad_norm is returned without
+    a synchronisation.  The coefficient serves that one step.  Every other call is torch.nn.utils.clip_grad_norm_ itself.  With a
+    GradientAllReducer the norm belongs to the REDUCED arena, which exists only inside step(): use FlatAdam.set_grad_clip there."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    kind = _norm_kind(norm_type)
+    try:
+        mn = float(max_norm)
+    except (TypeError, ValueError):
+        mn = -1.0
+    if kind is not None and not error_if_nonfinite and 0.0 < mn < float("inf"):
+        opt = _flat_owner(parameters)
+        if opt is not None and not opt._reducer_attached:
+            out = opt._clip_now(mn, kind)
+            if out is not None:
+                return out
+    return _torch_clip_grad_norm_(parameters, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
 
 
 class FlatAdamW(FlatAdam):

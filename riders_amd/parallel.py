@@ -154,6 +154,7 @@ class GradientAllReducer(object):
             self.rest.append((pos, optimizer.numel))
         self.buckets = [b for rs in list(self.stage_ranges.values()) + [self.rest] for b in self._split(rs)]
         optimizer.grad_scale = 1.0 / self.world
+        optimizer._reducer_attached = True      # riders_amd.clip_grad_norm_ hands such an optimizer to torch: the norm belongs after reduce()
         self._handles = []
         self._done = set()
         self.log = []      # (tag, start, end) of every all-reduce of the current / last finished step: test / debugging aid
@@ -166,6 +167,7 @@ class GradientAllReducer(object):
 
     def close(self):
         engine.remove_stage_hook(self.on_stage)
+        self.opt._reducer_attached = False
 
     def broadcast_parameters(self, src=0):
         if self.comm is not None:
