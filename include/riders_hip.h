@@ -349,6 +349,27 @@ int rd_linear_attention_fwd(const void* q, const void* k, const void* v, void* o
 int rd_linear_attention_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
                             int32_t N, int32_t L, int32_t S, int32_t H, int32_t ldq, int32_t ldk, int32_t ldv,
                             int32_t ldo, float eps, int32_t dtype, void* stream);
+/* the same with token masks (reference :33-37): q_mask [N][L], kv_mask [N][S], contiguous uint8 (the storage of a torch.bool tensor), nonzero =
+ * valid, either may be NULL = all valid.  A masked query row is Q = 0, a masked key row K = 0 and V = 0, the divisor stays S: masked query rows
+ * of out and dq, and masked key rows of dk and dv, are exact zeros.  Both masks NULL: bit-identical to the entries above. */
+int rd_linear_attention_masked_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask,
+                                   const uint8_t* kv_mask, int32_t N, int32_t L, int32_t S, int32_t H, int32_t ldq, int32_t ldk,
+                                   int32_t ldv, int32_t ldo, float eps, int32_t dtype, void* stream);
+int rd_linear_attention_masked_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
+                                   const uint8_t* q_mask, const uint8_t* kv_mask, int32_t N, int32_t L, int32_t S, int32_t H,
+                                   int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, float eps, int32_t dtype, void* stream);
+
+/* ---- softmax ('full') attention -- RCNet/linear_attention.py:49-80 --------------------------------
+ * out = softmax(scale * q k^T over the admissible keys) v, same layout and limits as the linear entries; masks as above, a pair (l, s) is
+ * admissible iff both tokens are valid.  A query row with no admissible key is DEFINED here (the reference gives NaN): its out row and its dq
+ * row are exact zeros and it adds nothing to dk / dv; dk and dv rows of masked keys are exact zeros.  The backward recomputes the attention
+ * from q, k, v.  Asynchronous on `stream`, no allocation, no host synchronisation. */
+int rd_full_attention_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask, const uint8_t* kv_mask,
+                          int32_t N, int32_t L, int32_t S, int32_t H, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
+                          float scale, int32_t dtype, void* stream);
+int rd_full_attention_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
+                          const uint8_t* q_mask, const uint8_t* kv_mask, int32_t N, int32_t L, int32_t S, int32_t H, int32_t ldq,
+                          int32_t ldk, int32_t ldv, int32_t ldo, float scale, int32_t dtype, void* stream);
 
 /* ---- pooling -- RCNet/networks.py:73-76 (MaxPool2d) and :418-433 (torchvision.ops.roi_pool) -------- */
 int rd_maxpool_fwd(const void* x, void* out, uint8_t* argmax, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH,

@@ -630,6 +630,38 @@ int rd_linear_attention_bwd(const void* q, const void* k, const void* v, const v
   RD_NS(dtype, launch_linear_attention_bwd)(q, k, v, dout, dq, dk, dv, N, L, Sx, H, ldq, ldk, ldv, ldo, eps, RD_DT(dtype), S(stream));
   return done("rd_linear_attention_bwd");
 }
+int rd_linear_attention_masked_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask, const uint8_t* kv_mask,
+                                   int32_t N, int32_t L, int32_t Sx, int32_t H, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
+                                   float eps, int32_t dtype, void* stream) {
+  if (!q || !k || !v || !out || !dt_ok(dtype)) return fail("linear_attention_masked_fwd: bad args");
+  if (L <= 0 || Sx <= 0 || L > 32 || Sx > 32) return fail("linear_attention_masked: L,S must be in 1..32 (got %d,%d)", L, Sx);
+  RD_NS(dtype, launch_linear_attention_masked_fwd)(q, k, v, out, q_mask, kv_mask, N, L, Sx, H, ldq, ldk, ldv, ldo, eps, RD_DT(dtype), S(stream));
+  return done("rd_linear_attention_masked_fwd");
+}
+int rd_linear_attention_masked_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
+                                   const uint8_t* q_mask, const uint8_t* kv_mask, int32_t N, int32_t L, int32_t Sx, int32_t H, int32_t ldq,
+                                   int32_t ldk, int32_t ldv, int32_t ldo, float eps, int32_t dtype, void* stream) {
+  if (!q || !k || !v || !dout || !dq || !dk || !dv || !dt_ok(dtype)) return fail("linear_attention_masked_bwd: bad args");
+  if (L <= 0 || Sx <= 0 || L > 32 || Sx > 32) return fail("linear_attention_masked: L,S must be in 1..32 (got %d,%d)", L, Sx);
+  RD_NS(dtype, launch_linear_attention_masked_bwd)(q, k, v, dout, dq, dk, dv, q_mask, kv_mask, N, L, Sx, H, ldq, ldk, ldv, ldo, eps, RD_DT(dtype), S(stream));
+  return done("rd_linear_attention_masked_bwd");
+}
+int rd_full_attention_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask, const uint8_t* kv_mask, int32_t N,
+                          int32_t L, int32_t Sx, int32_t H, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, float scale, int32_t dtype,
+                          void* stream) {
+  if (!q || !k || !v || !out || !dt_ok(dtype)) return fail("full_attention_fwd: bad args");
+  if (L <= 0 || Sx <= 0 || L > 32 || Sx > 32) return fail("full_attention: L,S must be in 1..32 (got %d,%d)", L, Sx);
+  RD_NS(dtype, launch_full_attention_fwd)(q, k, v, out, q_mask, kv_mask, N, L, Sx, H, ldq, ldk, ldv, ldo, scale, RD_DT(dtype), S(stream));
+  return done("rd_full_attention_fwd");
+}
+int rd_full_attention_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv, const uint8_t* q_mask,
+                          const uint8_t* kv_mask, int32_t N, int32_t L, int32_t Sx, int32_t H, int32_t ldq, int32_t ldk, int32_t ldv,
+                          int32_t ldo, float scale, int32_t dtype, void* stream) {
+  if (!q || !k || !v || !dout || !dq || !dk || !dv || !dt_ok(dtype)) return fail("full_attention_bwd: bad args");
+  if (L <= 0 || Sx <= 0 || L > 32 || Sx > 32) return fail("full_attention: L,S must be in 1..32 (got %d,%d)", L, Sx);
+  RD_NS(dtype, launch_full_attention_bwd)(q, k, v, dout, dq, dk, dv, q_mask, kv_mask, N, L, Sx, H, ldq, ldk, ldv, ldo, scale, RD_DT(dtype), S(stream));
+  return done("rd_full_attention_bwd");
+}
 
 int rd_maxpool_fwd(const void* x, void* out, uint8_t* arg, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW,
                    int32_t k, int32_t s, int32_t p, int32_t dtype, void* stream) {

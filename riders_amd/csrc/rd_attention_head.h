@@ -36,15 +36,15 @@ struct AttnSmem {
   float ksum[16], dksum[16], dden[MAXR], zinv[MAXR];
 };
 
-template <typename T>
+template <typename T, bool MASK = false>
 __device__ __forceinline__ void stage_head(const T* __restrict__ src, int64_t row0, int ld, int col0, int rows, float* dst,
-                                            int mode, float scale, bool active) {
-  // mode 0: raw*scale, mode 1: elu(x)+1
+                                            int mode, float scale, bool active, const uint8_t* __restrict__ mask = nullptr) {
+  // mode 0: raw*scale, mode 1: elu(x)+1; MASK: rows whose byte in mask[row0 + r] is zero are staged as zeros (mask NULL: none)
   const int lane = threadIdx.x & 63;
   for (int idx = lane; idx < MAXR * 16; idx += 64) {
     int r = idx >> 4, c = idx & 15;
     float x = 0.f;
-    if (active && r < rows) {
+    if (active && r < rows && (!MASK || mask == nullptr || mask[row0 + r] != 0)) {
       x = Elem<T>::ld(src + (row0 + r) * ld + col0 + c);
       x = mode ? (x > 0.f ? x + 1.f : __expf(x)) : x * scale;
     }
@@ -60,11 +60,17 @@ __device__ __forceinline__ void stage_head(const T* __restrict__ src, int64_t ro
 // L / S zero) and ordered them with a wave_sync(): no staging loads (rd_loftr.hip: the wave that owns head h is the wave whose projection
 // GEMM tile IS head h, so its accumulators go straight into its scratch).
 // PRED (backward only): s.d (the gradient of this head's attention output, rows beyond L zero) is already in place likewise.
-template <typename T, bool BWD, typename Hook, bool PRE = false, bool PRED = false>
+// MASK (compile time, default off: the unmasked instantiations are untouched): qm [N][L] / km [N][S] are token masks (uint8, nonzero = valid,
+// either may be NULL = all valid), applied as the reference does (RCNet/linear_attention.py:33-37): a masked query row is staged as Q = 0, a
+// masked key row as K = 0 and V = 0, each on its own and after the feature map; the divisor stays S.  A masked query row's normaliser would
+// be 1 / eps, whose square overflows at eps = 1e-30 just as the padded rows' does: its Z is stored as 0 instead, which makes its output row,
+// its dP and its dden exact zeros, and the guard of the dKsum sum covers it.  Not combined with PRE / PRED.
+template <typename T, bool BWD, typename Hook, bool PRE = false, bool PRED = false, bool MASK = false>
 __device__ __forceinline__ void attn_head(AttnSmem& s, const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                           const T* __restrict__ dout, T* __restrict__ out, T* __restrict__ dq, T* __restrict__ dk,
                                           T* __restrict__ dv, int n, int h, bool active, int L, int S, int ldq, int ldk, int ldv,
-                                          int ldo, float eps, Hook after_loads, T* lds_out = nullptr, int ldl = 0) {
+                                          int ldo, float eps, Hook after_loads, T* lds_out = nullptr, int ldl = 0,
+                                          const uint8_t* __restrict__ qm = nullptr, const uint8_t* __restrict__ km = nullptr) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, g = lane >> 4;
   const int col0 = h * 16;
@@ -83,6 +89,7 @@ __device__ __forceinline__ void attn_head(AttnSmem& s, const T* __restrict__ q, 
     // it was the whole cost of the attention phase inside the fused LoFTR layer)
     constexpr int SPR = 16 / VE, NIT = MAXR * SPR / 64;   // slots per row, slots per lane (1 for bf16, 2 for fp32)
     float xq[NIT][VE], xk[NIT][VE], xv[NIT][VE], xd[BWD ? NIT : 1][VE];
+    bool mq[NIT], mk[NIT];                 // MASK: validity of the slot's query / key row
     const int64_t nn = active ? n : 0;     // inactive waves read sequence 0 / head 0 and discard: no branch around the loads
     const int cc0 = active ? col0 : 0;     // (a load under a condition is waited for at the join, one round trip per tensor)
 #pragma unroll
@@ -98,6 +105,7 @@ __device__ __forceinline__ void attn_head(AttnSmem& s, const T* __restrict__ q, 
       rd::ldv(v + (nn * S + rs) * ldv + cc0 + c, xv[i]);
       if (BWD && !PRED) rd::ldv(dout + (nn * L + rl) * ldo + cc0 + c, xd[i]);
 #endif
+      if (MASK) { mq[i] = qm == nullptr || qm[nn * L + rl] != 0; mk[i] = km == nullptr || km[nn * S + rs] != 0; }
     }
     sched_fence();
     after_loads();
@@ -105,19 +113,20 @@ __device__ __forceinline__ void attn_head(AttnSmem& s, const T* __restrict__ q, 
     for (int i = 0; i < NIT; i++) {
       const int idx = lane + 64 * i, rr = idx / SPR, c = (idx - rr * SPR) * VE;
       const bool okq = active && rr < L, okk = active && rr < S;
+      const bool okqm = MASK ? (okq && mq[i]) : okq, okkm = MASK ? (okk && mk[i]) : okk;   // what is staged as zero (dout is not masked)
 #pragma unroll
       for (int e = 0; e < VE; e++) {
         const float a = xq[i][e], b = xk[i][e];
-        s.q[rr * LD + c + e] = okq ? (a > 0.f ? a + 1.f : __expf(a)) : 0.f;
-        s.k[rr * LD + c + e] = okk ? (b > 0.f ? b + 1.f : __expf(b)) : 0.f;
-        s.v[rr * LD + c + e] = okk ? xv[i][e] * (1.f / fS) : 0.f;
+        s.q[rr * LD + c + e] = okqm ? (a > 0.f ? a + 1.f : __expf(a)) : 0.f;
+        s.k[rr * LD + c + e] = okkm ? (b > 0.f ? b + 1.f : __expf(b)) : 0.f;
+        s.v[rr * LD + c + e] = okkm ? xv[i][e] * (1.f / fS) : 0.f;
         if (BWD && !PRED) s.d[rr * LD + c + e] = okq ? xd[i][e] * 1.f : 0.f;
       }
     }
   } else {
-    stage_head<T>(q, (int64_t)n * L, ldq, col0, L, s.q, 1, 1.f, active);
-    stage_head<T>(k, (int64_t)n * S, ldk, col0, S, s.k, 1, 1.f, active);
-    stage_head<T>(v, (int64_t)n * S, ldv, col0, S, s.v, 0, 1.f / fS, active);
+    stage_head<T, MASK>(q, (int64_t)n * L, ldq, col0, L, s.q, 1, 1.f, active, qm);
+    stage_head<T, MASK>(k, (int64_t)n * S, ldk, col0, S, s.k, 1, 1.f, active, km);
+    stage_head<T, MASK>(v, (int64_t)n * S, ldv, col0, S, s.v, 0, 1.f / fS, active, km);
     if (BWD && !PRED) stage_head<T>(dout, (int64_t)n * L, ldo, col0, L, s.d, 0, 1.f, active);
     after_loads();
   }
@@ -146,7 +155,9 @@ __device__ __forceinline__ void attn_head(AttnSmem& s, const T* __restrict__ q, 
   if (lane < MAXR) {
     float den = eps;
     for (int dd = 0; dd < 16; dd++) den += s.q[lane * LD + dd] * s.ksum[dd];
-    s.zinv[lane] = 1.f / den;
+    float zi = 1.f / den;
+    if (MASK) { if (qm != nullptr && qm[(int64_t)(active ? n : 0) * L + min(lane, L - 1)] == 0) zi = 0.f; }   // a masked query row: Z = 0
+    s.zinv[lane] = zi;
   }
   wave_sync();
   f32x4 P[2]; float Z[2][4];
@@ -214,7 +225,7 @@ __device__ __forceinline__ void attn_head(AttnSmem& s, const T* __restrict__ q, 
       for (int l = 0; l < MAXR; l++) { dx[l] = s.dden[l]; qx[l] = s.q[l * LD + lane]; }
       float t = 0.f;
 #pragma unroll
-      for (int l = 0; l < MAXR; l++) t += (l < L ? dx[l] : 0.f) * qx[l];
+      for (int l = 0; l < MAXR; l++) t += ((l < L && (!MASK || s.zinv[l] != 0.f)) ? dx[l] : 0.f) * qx[l];   // (MASK: Z = 0 marks a masked query row)
       s.dksum[lane] = t;
     }
   }

@@ -159,6 +159,19 @@ void launch_linear_attention_fwd(const void* q, const void* k, const void* v, vo
 void launch_linear_attention_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk,
                                  void* dv, int N, int L, int S, int H, int ldq, int ldk, int ldv, int ldo, float eps,
                                  int dtype, hipStream_t st);
+void launch_linear_attention_masked_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask,
+                                        const uint8_t* kv_mask, int N, int L, int S, int H, int ldq, int ldk, int ldv, int ldo,
+                                        float eps, int dtype, hipStream_t st);
+void launch_linear_attention_masked_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk,
+                                        void* dv, const uint8_t* q_mask, const uint8_t* kv_mask, int N, int L, int S, int H, int ldq,
+                                        int ldk, int ldv, int ldo, float eps, int dtype, hipStream_t st);
+
+// rd_attention_full.hip
+void launch_full_attention_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask, const uint8_t* kv_mask,
+                               int N, int L, int S, int H, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, hipStream_t st);
+void launch_full_attention_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
+                               const uint8_t* q_mask, const uint8_t* kv_mask, int N, int L, int S, int H, int ldq, int ldk, int ldv,
+                               int ldo, float scale, int dtype, hipStream_t st);
 
 // rd_loss.hip
 void launch_rcnet_labels(const float* gt, const float* points, float* label, float* valid, int R, int HW, float thr,

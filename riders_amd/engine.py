@@ -2013,13 +2013,27 @@ def layernorm(x, ln, residual=None):
     return out
 
 
-def linear_attention(q, k, v, N, Lq, S, H, eps=1e-6):
-    """q (N*L, H*16), k/v (N*S, H*16) token matrices -> (N*L, H*16)."""
+def token_mask(mask, N, Lq, dev):
+    """a [N, L] token mask as the kernels read it: contiguous torch.bool on the device (True = valid); other dtypes are converted with != 0, once"""
+    if mask is None:
+        return None
+    if mask.dtype != torch.bool:
+        mask = mask != 0
+    assert tuple(mask.shape) == (N, Lq), "token mask must be [N, L] = %s, got %s" % ((N, Lq), tuple(mask.shape))
+    return mask.to(dev).contiguous()
+
+
+def _attention_op(name, q, k, v, N, Lq, S, H, scalar, q_mask, kv_mask):
+    """rd_<name>_fwd now, rd_<name>_bwd on the tape (it recomputes from q, k, v); the two mask pointers go in front of N where given"""
     lib, t, dt, st = L(), tape(), rd_of(q), _stream(q)
     C = q.shape[1]
-    assert C == H * 16, "linear_attention kernel is specialised for head dim 16"
+    assert C == H * 16, "the attention kernels are specialised for head dim 16"
+    masks = () if q_mask is None and kv_mask is None and name == "linear_attention" else (_p(q_mask), _p(kv_mask))
+    if masks and name == "linear_attention":
+        name = "linear_attention_masked"
+    fwd, bwd = getattr(lib, "rd_%s_fwd" % name), getattr(lib, "rd_%s_bwd" % name)
     out = torch.empty_like(q)
-    _chk(lib.rd_linear_attention_fwd(_p(q), _p(k), _p(v), _p(out), N, Lq, S, H, C, C, C, C, eps, dt, st), "rd_linear_attention_fwd")
+    _chk(fwd(_p(q), _p(k), _p(v), _p(out), *masks, N, Lq, S, H, C, C, C, C, scalar, dt, st), "rd_%s_fwd" % name)
     if t is not None and t.requires(q, k, v):
         t.mark(out)
 
@@ -2028,13 +2042,25 @@ def linear_attention(q, k, v, N, Lq, S, H, eps=1e-6):
             if g is None:
                 return
             dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-            _chk(lib.rd_linear_attention_bwd(_p(q), _p(k), _p(v), _p(g), _p(dq), _p(dk), _p(dv), N, Lq, S, H, C, C, C, C, eps, dt, st),
-                 "rd_linear_attention_bwd")
+            mb = (_p(q_mask), _p(kv_mask)) if masks else ()      # (taken from the tensors again: the closure keeps them alive until here)
+            _chk(bwd(_p(q), _p(k), _p(v), _p(g), _p(dq), _p(dk), _p(dv), *mb, N, Lq, S, H, C, C, C, C, scalar, dt, st), "rd_%s_bwd" % name)
             t.add_grad(q, dq)
             t.add_grad(k, dk)
             t.add_grad(v, dv)
         t.record(backward)
     return out
+
+
+def linear_attention(q, k, v, N, Lq, S, H, eps=1e-6, q_mask=None, kv_mask=None):
+    """q (N*L, H*16), k/v (N*S, H*16) token matrices -> (N*L, H*16).  q_mask [N, L] / kv_mask [N, S] (token_mask()): given either, the masked
+    entries run (masked query rows Q = 0, masked key rows K = V = 0, divisor S); with none, rd_linear_attention_fwd / _bwd as ever."""
+    return _attention_op("linear_attention", q, k, v, N, Lq, S, H, eps, q_mask, kv_mask)
+
+
+def full_attention(q, k, v, N, Lq, S, H, q_mask=None, kv_mask=None):
+    """softmax(q k^T / sqrt(16)) v over the admissible keys (rd_attention_full.hip); token matrices and masks as linear_attention.  A query
+    row with no admissible key comes out as zeros (the reference: NaN)."""
+    return _attention_op("full_attention", q, k, v, N, Lq, S, H, 0.25, q_mask, kv_mask)
 
 
 def _common_base(a, b):
