@@ -447,6 +447,26 @@ int rd_depth_quantize_u16(const float* z, uint16_t* out, int64_t n, float multip
 /* RCNet/run_rcnet_zju.py:253 np.sum(output_depth) == 0 test of the threshold-retry loop: double-precision sum of n floats */
 int rd_sum_f32(const float* x, int64_t n, double* out, void* stream);
 
+/* ---- RC-Net inference over frame batches: the fusion of RCNet/run_rcnet_zju.py:242-264 for F frames with ragged point counts ------------------
+   crops [R][PH][PW] in `dtype`, points [R][3] fp32 in padded coordinates, frame_start int32 [F + 1] ON THE DEVICE, ascending, frame_start[0] = 0,
+   frame_start[F] = R: crop c belongs to frame f iff frame_start[f] <= c < frame_start[f + 1].  Index rules are rd_scatter_crops'.
+   rd_frame_thresholds (two launches, no host read): rmax[f] = the largest response of frame f that is pasted inside the un-padded H x W image (NaN
+   and values <= 0 ignored, 0 if there is none); for rmax[f] > 0: { double t = start; n = 0; while ((float)t > rmax[f]) { t -= step; ++n; } thr[f] =
+   (float)t; retries[f] = n; } -- the threshold at which the reference's retry loop stops, given positive radar depths; for rmax[f] <= 0 (the
+   reference never ends): thr[f] = (float)start, retries[f] = -1 and the sticky word *flag becomes 1 (the caller zeroes it once and after reading it).
+   Refused: step <= 0, a non-finite start, start / step > 4096 (these bound the device loop), odd PH / PW, F < 0, null pointers when R > 0.
+   workspace: rd_frame_thresholds_ws_bytes(R) bytes of device memory (per-block partial maxima; no zeroing needed). */
+int64_t rd_frame_thresholds_ws_bytes(int32_t R);
+int rd_frame_thresholds(const void* crops, const float* points, const int32_t* frame_start, int32_t R, int32_t F, int32_t PH, int32_t PW,
+                        int32_t H, int32_t W, double start, double step, float* workspace, float* rmax, float* thr, int32_t* retries,
+                        int32_t* flag, int32_t dtype, void* stream);
+/* depth / response [F][H][W] fp32: for every frame bit-identical to rd_scatter_crops on the frame's slice of crops / points with response_thr =
+   thr[f] (thr: DEVICE float [F]); a frame without points is written as zeros.  There is no limit on the points of a frame: a block walks them in
+   chunks of rd_scatter_frames_chunk() and carries its sums across chunks. */
+int32_t rd_scatter_frames_chunk(void);
+int rd_scatter_crops_frames(const void* crops, const float* points, const int32_t* frame_start, const float* thr, float* depth, float* response,
+                            int32_t R, int32_t F, int32_t PH, int32_t PW, int32_t H, int32_t W, int32_t dtype, void* stream);
+
 /* ---- batch augmentation on the device -- RCNet/rcnet_transforms.py:58-240 as configured by train_rcnet_zju.py:52-59 ---------------------
    params: [B][8] floats = (do_brightness, factor, do_contrast, factor, do_saturation, factor, do_hflip, do_vflip), drawn by the host in the
    reference's order.  image (B,3,H,W) float 0..255.  Step 1 sums the gray values the contrast blend needs ([B][32] int64 partials, exact). */

@@ -844,6 +844,35 @@ int rd_sum_f32(const float* x, int64_t n, double* out, void* stream) {
   return done("rd_sum_f32");
 }
 
+int32_t rd_scatter_frames_chunk(void) { return rd::scatter_frames_chunk(); }
+int64_t rd_frame_thresholds_ws_bytes(int32_t R) { return rd::frame_thresholds_ws_bytes(R); }
+int rd_frame_thresholds(const void* crops, const float* points, const int32_t* frame_start, int32_t R, int32_t F, int32_t PH, int32_t PW,
+                        int32_t H, int32_t W, double start, double step, float* workspace, float* rmax, float* thr, int32_t* retries,
+                        int32_t* flag, int32_t dtype, void* stream) {
+  if (!dt_ok(dtype) || F < 0 || R < 0 || PH <= 0 || PW <= 0 || H <= 0 || W <= 0) return fail("frame_thresholds: bad args");
+  if ((PH & 1) || (PW & 1)) return fail("frame_thresholds: patch size must be even (reference uses patch//2 on both sides)");
+  if (!(step > 0.0)) return fail("frame_thresholds: the threshold step must be positive");
+  if (!__builtin_isfinite(start) || !__builtin_isfinite(step)) return fail("frame_thresholds: start / step must be finite");
+  if (start / step > 4096.0) return fail("frame_thresholds: start / step above 4096 (the device loop is bounded by it)");
+  if (F == 0) return 0;
+  if (!frame_start || !rmax || !thr || !retries || !flag) return fail("frame_thresholds: null pointer");
+  if (R > 0 && (!crops || !points || !workspace)) return fail("frame_thresholds: null pointer");
+  RD_NS(dtype, launch_frame_thresholds)(crops, points, frame_start, R, F, PH, PW, H, W, start, step, workspace, rmax, thr, retries, flag,
+                                        RD_DT(dtype), S(stream));
+  return done("rd_frame_thresholds");
+}
+int rd_scatter_crops_frames(const void* crops, const float* points, const int32_t* frame_start, const float* thr, float* depth, float* response,
+                            int32_t R, int32_t F, int32_t PH, int32_t PW, int32_t H, int32_t W, int32_t dtype, void* stream) {
+  if (!dt_ok(dtype) || F < 0 || R < 0 || PH <= 0 || PW <= 0 || H <= 0 || W <= 0) return fail("scatter_crops_frames: bad args");
+  if ((PH & 1) || (PW & 1)) return fail("scatter_crops_frames: patch size must be even (reference uses patch//2 on both sides)");
+  if (F > 65535 || (H + 3) / 4 > 65535) return fail("scatter_crops_frames: more than 65535 frames or tile rows in one launch");
+  if (F == 0) return 0;
+  if (!frame_start || !thr || !depth || !response) return fail("scatter_crops_frames: null pointer");
+  if (R > 0 && (!crops || !points)) return fail("scatter_crops_frames: null pointer");
+  RD_NS(dtype, launch_scatter_crops_frames)(crops, points, frame_start, thr, depth, response, F, PH, PW, H, W, RD_DT(dtype), S(stream));
+  return done("rd_scatter_crops_frames");
+}
+
 int rd_augment_gray_partials(const float* image, int32_t B, int32_t H, int32_t W, const float* params, int64_t* partial, void* stream) {
   if (!image || !params || !partial || B <= 0 || H <= 0 || W <= 0) return fail("augment_gray_partials: bad args");
   rd::launch_augment_gray_partials(image, B, H, W, params, (long long*)partial, S(stream));

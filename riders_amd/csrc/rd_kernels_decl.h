@@ -190,6 +190,14 @@ void launch_boxes_to_rois(const float* boxes, float* rois, int B, int K, int fir
 void launch_depth_quantize_u16(const float* z, unsigned short* out, int64_t n, float multiplier, hipStream_t st);
 void launch_sum_f32(const float* x, int64_t n, double* out, hipStream_t st);
 
+// rd_infer.hip
+int scatter_frames_chunk();
+int64_t frame_thresholds_ws_bytes(int R);
+void launch_frame_thresholds(const void* crops, const float* points, const int* frame_start, int R, int F, int PH, int PW, int H, int W,
+                             double start, double step, float* ws, float* rmax, float* thr, int* retries, int* flag, int dtype, hipStream_t st);
+void launch_scatter_crops_frames(const void* crops, const float* points, const int* frame_start, const float* thr, float* depth, float* response,
+                                 int F, int PH, int PW, int H, int W, int dtype, hipStream_t st);
+
 // rd_augment.hip
 void launch_augment_gray_partials(const float* image, int B, int H, int W, const float* params, long long* partial, hipStream_t st);
 void launch_augment_image(const float* image, int B, int H, int W, const float* params, const long long* partial, void* out, int dtype, float scale, float shift, hipStream_t st);
