@@ -698,6 +698,14 @@ int rd_bilinear_bwd(const void* dy, void* dx, int32_t N, int32_t H, int32_t W, i
 int rd_sml_head_fwd(const void* out, const float* d, float* pred, int64_t n, float hi, float lo, int32_t dtype, void* stream);
 int rd_sml_head_bwd(const void* out, const float* d, const float* dpred, void* dout, int64_t n, float hi, float lo, int32_t dtype,
                     void* stream);
+/* modules/midas/midas_net_custom.py:240-257 (MidasNet_small_depth): pred = relu(1+out), then pred > hi -> hi, pred < lo -> lo (hi = 1/min_pred,
+   lo = 1/max_pred, < 0 disables that clamp); out in its storage type, pred fp32.  The backward writes dout (out's type) = dpred where 1+out > 0
+   and neither clamp replaced the value (strict comparisons: a value equal to a bound keeps its gradient), 0 elsewhere. */
+int rd_sml_depth_head_fwd(const void* out, float* pred, int64_t n, float hi, float lo, int32_t dtype, void* stream);
+int rd_sml_depth_head_bwd(const void* out, const float* dpred, void* dout, int64_t n, float hi, float lo, int32_t dtype, void* stream);
+/* train_zju.py:158-165, :363-364: torch.nn.MaxPool2d(k, stride=1, padding=k/2) on (N,1,H,W) fp32 maps, the maximum over the window clipped to
+   the image; k odd in 1..31 (k = 1 copies); x must not alias y */
+int rd_maxpool_dilate(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t k, void* stream);
 /* train_zju.py:355-356: out = 1/x (dy == NULL) or dx = -dy/x^2 */
 int rd_reciprocal(const float* x, const float* dy, float* out, int64_t n, void* stream);
 /* train_zju.py:246-343 + modules/estimator.py:146-176: per-sample bounded L1 scale fit of mono inverse depth to radar */

@@ -1183,6 +1183,31 @@ int rd_sml_head_bwd(const void* out, const float* d, const float* dpred, void* d
   RD_NS(dtype, launch_sml_head_bwd)(out, d, dpred, dout, n, hi, lo, RD_DT(dtype), S(stream));
   return done("rd_sml_head_bwd");
 }
+int rd_sml_depth_head_fwd(const void* out, float* pred, int64_t n, float hi, float lo, int32_t dtype, void* stream) {
+  if (!out || !pred) return fail("sml_depth_head_fwd: null pointer");
+  if (!dt_ok(dtype)) return fail("sml_depth_head_fwd: bad dtype %d", dtype);
+  if (n < 0) return fail("sml_depth_head_fwd: negative size");
+  if (n == 0) return 0;
+  RD_NS(dtype, launch_sml_depth_head_fwd)(out, pred, n, hi, lo, RD_DT(dtype), S(stream));
+  return done("rd_sml_depth_head_fwd");
+}
+int rd_sml_depth_head_bwd(const void* out, const float* dpred, void* dout, int64_t n, float hi, float lo, int32_t dtype, void* stream) {
+  if (!out || !dpred || !dout) return fail("sml_depth_head_bwd: null pointer");
+  if (!dt_ok(dtype)) return fail("sml_depth_head_bwd: bad dtype %d", dtype);
+  if (n < 0) return fail("sml_depth_head_bwd: negative size");
+  if (n == 0) return 0;
+  RD_NS(dtype, launch_sml_depth_head_bwd)(out, dpred, dout, n, hi, lo, RD_DT(dtype), S(stream));
+  return done("rd_sml_depth_head_bwd");
+}
+int rd_maxpool_dilate(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t k, void* stream) {
+  if (!x || !y) return fail("maxpool_dilate: null pointer");
+  if (x == y) return fail("maxpool_dilate: x must not alias y");
+  if (k < 1 || k > 31 || !(k & 1)) return fail("maxpool_dilate: kernel size must be odd in 1..31 (got %d)", k);
+  if (N < 0 || H < 0 || W < 0) return fail("maxpool_dilate: negative size");
+  if (N == 0 || H == 0 || W == 0) return 0;
+  rd::launch_maxpool_dilate(x, y, N, H, W, k, S(stream));
+  return done("rd_maxpool_dilate");
+}
 int rd_reciprocal(const float* x, const float* dy, float* out, int64_t n, void* stream) {
   if (!x || !out) return fail("reciprocal: null pointer");
   if (n == 0) return 0;

@@ -295,4 +295,9 @@ void launch_sml_unsup_bwd(const float* pred, const float* image, const unsigned 
 void launch_bicubic(const float* x, float* y, int N, int H, int W, int OH, int OW, hipStream_t st);
 void launch_depth_metrics(const float* out, const float* gt, int N, int HW, float dmin, float dmax, double* res, hipStream_t st);
 
+// rd_sml_depth.hip
+void launch_sml_depth_head_fwd(const void* out, float* pred, int64_t n, float hi, float lo, int dtype, hipStream_t st);
+void launch_sml_depth_head_bwd(const void* out, const float* dpred, void* dout, int64_t n, float hi, float lo, int dtype, hipStream_t st);
+void launch_maxpool_dilate(const float* x, float* y, int N, int H, int W, int k, hipStream_t st);
+
 }  // namespace rd

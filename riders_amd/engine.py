@@ -2614,6 +2614,39 @@ def sml_head(out, d, min_pred, max_pred):
     return pred
 
 
+def sml_depth_head(out, min_pred, max_pred):
+    """pred = relu(1 + out) with the in-place clamps of midas_net_custom.py:240-257 (MidasNet_small_depth); out (N,H,W,1) -> pred fp32."""
+    lib, t, dt, st = L(), tape(), rd_of(out), _stream(out)
+    hi = 1.0 / min_pred if min_pred is not None else -1.0
+    lo = 1.0 / max_pred if max_pred is not None else -1.0
+    pred = torch.empty(out.shape, dtype=torch.float32, device=out.device)
+    n = out.numel()
+    _chk(lib.rd_sml_depth_head_fwd(_p(out), _p(pred), n, hi, lo, dt, st), "rd_sml_depth_head_fwd")
+    if t is not None and t.requires(out):
+        t.mark(pred)
+
+        def backward():
+            g = t.pop_grad(pred)
+            if g is None:
+                return
+            do = torch.empty_like(out)
+            _chk(lib.rd_sml_depth_head_bwd(_p(out), _p(g), _p(do), n, hi, lo, dt, st), "rd_sml_depth_head_bwd")
+            t.add_grad(out, do)
+        t.record(backward)
+    return pred
+
+
+def dilate_max(x, k):
+    """torch.nn.MaxPool2d(k, stride=1, padding=k // 2) on (N,1,H,W) fp32 maps (train_zju.py:158-165: ground truth, so no backward)."""
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+        raise ValueError("dilate_max: expected an (N,1,H,W) float32 map, got %s %s" % (tuple(x.shape), x.dtype))
+    x = x if x.is_contiguous() else x.contiguous()
+    N, _, H, W = x.shape
+    y = torch.empty_like(x)
+    _chk(L().rd_maxpool_dilate(_p(x), _p(y), N, H, W, int(k), _stream(x)), "rd_maxpool_dilate")
+    return y
+
+
 def reciprocal(x):
     lib, t, st = L(), tape(), _stream(x)
     out = torch.empty_like(x)

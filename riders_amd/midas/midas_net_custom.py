@@ -1,5 +1,5 @@
-"""MidasNet_small_videpth (Scale Map Learner) on MI355X; same constructor / forward(x, d) / state_dict keys as
-modules/midas/midas_net_custom.py:22-133.  The whole forward is one engine region."""
+"""MidasNet_small_videpth (Scale Map Learner) and MidasNet_small_depth (direct regression) on MI355X; same constructor / forward(x, d) /
+state_dict keys as modules/midas/midas_net_custom.py:22-133 and :136-257.  The whole forward is one engine region."""
 import math
 
 import torch
@@ -23,12 +23,16 @@ def weights_init(m):
         m.bias.data.zero_()
 
 
-class MidasNet_small_videpth(BaseModel):
+class _MidasNetSmall(BaseModel):
+    """What MidasNet_small_videpth and MidasNet_small_depth share (the reference repeats it, midas_net_custom.py:22-119 and :136-238):
+    constructor, backbone + decoder forward up to the 1-channel `out`, stage marks, BatchNorm counter bookkeeping.  A subclass supplies
+    `_head(out, d)` and `forward`."""
+
     def __init__(self, device='cpu', path=None, features=64, backbone="efficientnet_lite3", non_negative=False, exportable=True,
                  channels_last=False, align_corners=True, blocks={'expand': True}, in_channels=2, regress='r', min_pred=None,
                  max_pred=None):
         print("Loading weights: ", path)
-        super(MidasNet_small_videpth, self).__init__()
+        super(_MidasNetSmall, self).__init__()
         use_pretrained = False if path else True
         self.channels_last = channels_last
         self.blocks = blocks
@@ -64,8 +68,11 @@ class MidasNet_small_videpth(BaseModel):
             self.pretrained.layer1[1].num_batches_tracked += sp
             self.pretrained.layer1._stem_pending = 0
 
+    def _head(self, out, d):
+        raise NotImplementedError
+
     def _fwd(self, x, d):
-        """x (B,H,W,C) activation dtype, d (B,H,W,1) fp32 -> pred (B,H,W,1) fp32."""
+        """x (B,H,W,C) activation dtype, d (B,H,W,1) fp32 or None (a head that does not read it) -> pred (B,H,W,1) fp32."""
         c, bn = self.first[0], self.first[1]
         if efficientnet_lite3.bn_counts(bn):
             self._first_pending += 1
@@ -86,17 +93,7 @@ class MidasNet_small_videpth(BaseModel):
         path_2 = s.refinenet2._fwd(path_3, l2)
         path_1 = s.refinenet1._fwd(path_2, l1)
         out = s.output_conv._fwd(path_1)
-        return engine.sml_head(out, d, self.min_pred, self.max_pred)
-
-    def forward(self, x, d):
-        dd = d if d.is_contiguous() else d.contiguous()   # (B,1,H,W): C == 1, NCHW == NHWC in memory
-
-        def run(x, dd):
-            pred = self._fwd(engine.from_nchw(x), dd)
-            return engine.alias(pred, pred.view(dd.shape))
-        # (d is a region INPUT: a captured region -- engine.set_autograph -- reads it from a static tensor)
-        return engine.run_region(run, (x, dd), list(self.parameters()), graph_key=("MidasNet_small_videpth.forward", id(self), self.training, engine.bn_signature(self)),
-                                 on_replay=self._bn_replay)
+        return self._head(out, d)
 
     def _bn_replay(self, delta=1):
         """host-side bookkeeping of `delta` replayed forwards: the num_batches_tracked counters this module's _fwd bumps, per BatchNorm
@@ -111,10 +108,34 @@ class MidasNet_small_videpth(BaseModel):
             self.pretrained.layer1._stem_pending = getattr(self.pretrained.layer1, "_stem_pending", 0) + delta
 
 
-class MidasNet_small_depth(BaseModel):
-    """modules/midas/midas_net_custom.py:136-261, model_type 'midas-small-depth' (train_zju.py:180): an alternative head the ZJU configuration
-    never selects (out of scope).  The name exists because train_zju.py:14 / val_zju.py:17 import it next to
-    MidasNet_small_videpth; constructing it says so."""
+class MidasNet_small_videpth(_MidasNetSmall):
+    def _head(self, out, d):
+        return engine.sml_head(out, d, self.min_pred, self.max_pred)
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("MidasNet_small_depth ('midas-small-depth') is not on the RIDERS ZJU path; use MidasNet_small_videpth")
+    def forward(self, x, d):
+        dd = d if d.is_contiguous() else d.contiguous()   # (B,1,H,W): C == 1, NCHW == NHWC in memory
+
+        def run(x, dd):
+            pred = self._fwd(engine.from_nchw(x), dd)
+            return engine.alias(pred, pred.view(dd.shape))
+        # (d is a region INPUT: a captured region -- engine.set_autograph -- reads it from a static tensor)
+        return engine.run_region(run, (x, dd), list(self.parameters()), graph_key=("MidasNet_small_videpth.forward", id(self), self.training, engine.bn_signature(self)),
+                                 on_replay=self._bn_replay)
+
+
+class MidasNet_small_depth(_MidasNetSmall):
+    """modules/midas/midas_net_custom.py:136-257, model_type 'midas-small-depth' (train_zju.py:180-186): the direct-regression counterpart of the
+    scale-map model.  Same constructor arguments and defaults, same backbone and decoder, same 489 state_dict keys (a checkpoint of one class
+    loads into the other); the head predicts inverse depth itself, pred = relu(1 + out) clamped to [1/max_pred, 1/min_pred], instead of a
+    multiplier of `d`.  forward(x, d) keeps the reference's signature: `d` is ignored and may be None.  The whole forward is one engine
+    region with `x` as its only input."""
+
+    def _head(self, out, d):
+        return engine.sml_depth_head(out, self.min_pred, self.max_pred)
+
+    def forward(self, x, d=None):
+        def run(x):
+            pred = self._fwd(engine.from_nchw(x), None)
+            return engine.alias(pred, pred.view(x.shape[0], 1, x.shape[2], x.shape[3]))
+        return engine.run_region(run, (x,), list(self.parameters()), graph_key=("MidasNet_small_depth.forward", id(self), self.training, engine.bn_signature(self)),
+                                 on_replay=self._bn_replay)

@@ -9,7 +9,7 @@ import torch
 
 from . import engine
 from .loss import compute_loss
-from .midas.midas_net_custom import MidasNet_small_videpth
+from .midas.midas_net_custom import MidasNet_small_depth, MidasNet_small_videpth
 from .net_utils import OutlierRemoval
 
 # train_zju.py:429-487
@@ -30,7 +30,26 @@ def net_size(height, width, net_h=288, net_w=384, multiple=32):
 
 
 def build_model(device, cfg=ZJU_SML_CONFIG):
-    return MidasNet_small_videpth(device=device, in_channels=3, min_pred=cfg['min_pred'], max_pred=cfg['max_pred'])
+    """train_zju.py:174-186: model_type 'midas-small' (the scale-map model, default) or 'midas-small-depth' (direct regression)."""
+    model_type = cfg.get('model_type', 'midas-small')
+    if model_type == 'midas-small':
+        cls = MidasNet_small_videpth
+    elif model_type == 'midas-small-depth':
+        cls = MidasNet_small_depth
+    else:
+        raise NotImplementedError("model_type %r (this port has 'midas-small' and 'midas-small-depth'; train_zju.py:174-186)" % (model_type,))
+    return cls(device=device, in_channels=3, min_pred=cfg['min_pred'], max_pred=cfg['max_pred'])
+
+
+def gt_dilation_kernel_size(cfg):
+    """train_zju.py:158-165: ground_truth_dilation_kernel_size, active when > 1 (default -1) -> the kernel size or 0.  An even size is refused:
+    MaxPool2d(k, stride=1, padding=k // 2) then returns a map one pixel larger than the prediction and the reference's loss fails on the shapes."""
+    k = int(cfg.get('ground_truth_dilation_kernel_size', -1))
+    if k <= 1:
+        return 0
+    if k % 2 == 0:
+        raise ValueError("ground_truth_dilation_kernel_size must be odd (got %d)" % k)
+    return k
 
 
 def synthetic_batch(batch_size, height=288, width=384, seed=1234, device='cpu'):
@@ -108,6 +127,9 @@ def forward_loss(model, batch, cfg=ZJU_SML_CONFIG, outlier=None):
     sml_depth = engine.run_region(lambda p: engine.reciprocal(p), (pred,), [])
     w_u = cfg.get('w_unsupervised', 0.0)
     invalid = gt_r if w_u > 0.0 else None      # train_zju.py:361: the mask is gt <= 0 BEFORE outlier removal; the loss kernels apply the rule to the map itself
+    k_dil = gt_dilation_kernel_size(cfg)
+    if k_dil:      # train_zju.py:363-364: after `invalid` (taken from the undilated map), before the outlier removal
+        gt_r = engine.dilate_max(gt_r, k_dil)
     if outlier is not None:
         gt_r = outlier.remove_outliers(gt_r)
     loss, info = compute_loss(image=d_depth, output_depth=sml_depth, gt_interp=gt_r, gt_sparse=sgt_r, loss_func=cfg['loss_func'],
