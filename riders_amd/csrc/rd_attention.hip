@@ -57,34 +57,30 @@ static void launch_masked(const void* q, const void* k, const void* v, const voi
 }
 void launch_linear_attention_masked_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask, const uint8_t* kv_mask,
                                         int N, int L, int S, int H, int ldq, int ldk, int ldv, int ldo, float eps, int dtype, hipStream_t st) {
-  if (dtype == 0) launch_masked<float>(q, k, v, nullptr, out, nullptr, nullptr, nullptr, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, eps, false, st);
-  else launch_masked<bf16_t>(q, k, v, nullptr, out, nullptr, nullptr, nullptr, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, eps, false, st);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    launch_masked<T>(q, k, v, nullptr, out, nullptr, nullptr, nullptr, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, eps, false, st); });
 }
 void launch_linear_attention_masked_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
                                         const uint8_t* q_mask, const uint8_t* kv_mask, int N, int L, int S, int H, int ldq, int ldk, int ldv,
                                         int ldo, float eps, int dtype, hipStream_t st) {
-  if (dtype == 0) launch_masked<float>(q, k, v, dout, nullptr, dq, dk, dv, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, eps, true, st);
-  else launch_masked<bf16_t>(q, k, v, dout, nullptr, dq, dk, dv, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, eps, true, st);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    launch_masked<T>(q, k, v, dout, nullptr, dq, dk, dv, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, eps, true, st); });
 }
 
 void launch_linear_attention_fwd(const void* q, const void* k, const void* v, void* out, int N, int L, int S, int H, int ldq,
                                  int ldk, int ldv, int ldo, float eps, int dtype, hipStream_t st) {
   unsigned grid = (unsigned)cdiv((int64_t)N * H, 4);
   if (grid == 0) return;
-  if (dtype == 0)
-    hipLaunchKernelGGL((linear_attention_kernel<float, false>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k, (const float*)v, (const float*)nullptr, (float*)out, (float*)nullptr, (float*)nullptr, (float*)nullptr, N, L, S, H, ldq, ldk, ldv, ldo, eps);
-  else
-    hipLaunchKernelGGL((linear_attention_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)nullptr, (bf16_t*)out, (bf16_t*)nullptr, (bf16_t*)nullptr, (bf16_t*)nullptr, N, L, S, H, ldq, ldk, ldv, ldo, eps);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((linear_attention_kernel<T, false>), dim3(grid), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (const T*)nullptr, (T*)out, (T*)nullptr, (T*)nullptr, (T*)nullptr, N, L, S, H, ldq, ldk, ldv, ldo, eps); });
 }
 void launch_linear_attention_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
                                  int N, int L, int S, int H, int ldq, int ldk, int ldv, int ldo, float eps, int dtype,
                                  hipStream_t st) {
   unsigned grid = (unsigned)cdiv((int64_t)N * H, 4);
   if (grid == 0) return;
-  if (dtype == 0)
-    hipLaunchKernelGGL((linear_attention_kernel<float, true>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k, (const float*)v, (const float*)dout, (float*)nullptr, (float*)dq, (float*)dk, (float*)dv, N, L, S, H, ldq, ldk, ldv, ldo, eps);
-  else
-    hipLaunchKernelGGL((linear_attention_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, (bf16_t*)nullptr, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, N, L, S, H, ldq, ldk, ldv, ldo, eps);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((linear_attention_kernel<T, true>), dim3(grid), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (const T*)dout, (T*)nullptr, (T*)dq, (T*)dk, (T*)dv, N, L, S, H, ldq, ldk, ldv, ldo, eps); });
 }
 
 }  // namespace rd

@@ -266,14 +266,14 @@ static void launch_full(const void* q, const void* k, const void* v, const void*
 
 void launch_full_attention_fwd(const void* q, const void* k, const void* v, void* out, const uint8_t* q_mask, const uint8_t* kv_mask, int N,
                                int L, int S, int H, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, hipStream_t st) {
-  if (dtype == 0) launch_full<float>(q, k, v, nullptr, out, nullptr, nullptr, nullptr, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, scale, false, st);
-  else launch_full<bf16_t>(q, k, v, nullptr, out, nullptr, nullptr, nullptr, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, scale, false, st);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    launch_full<T>(q, k, v, nullptr, out, nullptr, nullptr, nullptr, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, scale, false, st); });
 }
 void launch_full_attention_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
                                const uint8_t* q_mask, const uint8_t* kv_mask, int N, int L, int S, int H, int ldq, int ldk, int ldv, int ldo,
                                float scale, int dtype, hipStream_t st) {
-  if (dtype == 0) launch_full<float>(q, k, v, dout, nullptr, dq, dk, dv, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, scale, true, st);
-  else launch_full<bf16_t>(q, k, v, dout, nullptr, dq, dk, dv, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, scale, true, st);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    launch_full<T>(q, k, v, dout, nullptr, dq, dk, dv, q_mask, kv_mask, N, L, S, H, ldq, ldk, ldv, ldo, scale, true, st); });
 }
 
 }  // namespace rd

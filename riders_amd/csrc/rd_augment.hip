@@ -150,8 +150,8 @@ void launch_augment_gray_partials(const float* image, int B, int H, int W, const
 void launch_augment_image(const float* image, int B, int H, int W, const float* params, const long long* partial, void* out, int dtype, float scale,
                           float shift, hipStream_t st) {
   const unsigned g = aug_grid((int64_t)B * H * W);
-  if (dtype == 0) hipLaunchKernelGGL((augment_image_kernel<float>), dim3(g), dim3(256), 0, st, image, B, H, W, params, partial, (float*)out, scale, shift);
-  else hipLaunchKernelGGL((augment_image_kernel<bf16_t>), dim3(g), dim3(256), 0, st, image, B, H, W, params, partial, (bf16_t*)out, scale, shift);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((augment_image_kernel<T>), dim3(g), dim3(256), 0, st, image, B, H, W, params, partial, (T*)out, scale, shift); });
 }
 void launch_augment_flip_labels(const float* lin, float* lout, int B, int K, int ph, int pw, float* boxes, const float* params, float n_width,
                                 hipStream_t st) {

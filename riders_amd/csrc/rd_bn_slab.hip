@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void bn_fwd_slab_kernel(const float* __restric
 // 15.6 -> 11.8 at 816), at 10 368 pixels (41 per thread) 16.7 -> 21.2 and 20.6 -> 51 us.  Default: >= 64 workgroups and <= 11 pixels per
 // thread; "bn_slab" (rd_set_option): 0 off, 2 = any channel count and up to 22 pixels per thread (tests).
 bool bn_slab_ok(int64_t pixels, int C, int dtype) {
-  const int ve = dtype == 0 ? 4 : 8, opt = rd_opt(OPT_BN_SLAB, 1);
+  const int ve = elem_vec(dtype), opt = rd_opt(OPT_BN_SLAB, 1);
   if (opt == 0 || pixels <= 0 || (C % ve) != 0) return false;
   if (opt == 2) return pixels <= 256 * 22;
   return pixels <= 256 * 11 && C / ve >= 64;
@@ -230,8 +230,8 @@ static void launch_bn_bwd_slab_t(const void* dz, const void* y, const float* mea
 }
 void launch_bn_bwd_slab(const void* dz, const void* y, const float* mean, const float* rstd, const float* scale, const float* shift, float* dgamma,
                         float* dbeta, int accumulate, void* dy, int64_t pixels, int C, int act, float slope, int dtype, hipStream_t st) {
-  if (dtype == 0) launch_bn_bwd_slab_t<float>(dz, y, mean, rstd, scale, shift, dgamma, dbeta, accumulate, dy, pixels, C, act, slope, st);
-  else launch_bn_bwd_slab_t<bf16_t>(dz, y, mean, rstd, scale, shift, dgamma, dbeta, accumulate, dy, pixels, C, act, slope, st);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    launch_bn_bwd_slab_t<T>(dz, y, mean, rstd, scale, shift, dgamma, dbeta, accumulate, dy, pixels, C, act, slope, st); });
 }
 template <typename T>
 static void launch_bn_fwd_slab_t(const float* stats, int rows, const void* y, const float* gamma, const float* beta, float eps, float momentum,
@@ -250,13 +250,13 @@ static void launch_bn_fwd_slab_t(const float* stats, int rows, const void* y, co
 void launch_bn_fwd_slab(const float* stats, int rows, const void* y, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
                         float* running_var, float* mean, float* rstd, float* scale, float* shift, void* out, int64_t pixels, int C, int act, float slope,
                         int dtype, hipStream_t st) {
-  if (dtype == 0) launch_bn_fwd_slab_t<float>(stats, rows, y, gamma, beta, eps, momentum, running_mean, running_var, mean, rstd, scale, shift, out, pixels, C, act, slope, st);
-  else launch_bn_fwd_slab_t<bf16_t>(stats, rows, y, gamma, beta, eps, momentum, running_mean, running_var, mean, rstd, scale, shift, out, pixels, C, act, slope, st);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    launch_bn_fwd_slab_t<T>(stats, rows, y, gamma, beta, eps, momentum, running_mean, running_var, mean, rstd, scale, shift, out, pixels, C, act, slope, st); });
 }
 const char* bn_slab_kernel_name(int which, int64_t pixels, int dtype, int act) {      // which 0 = forward, 1 = backward (as rocprofv3 prints them)
   static thread_local char buf[96];
   const int A = (act == 0 || act == 3) ? act : -1;
-  snprintf(buf, sizeof(buf), "%s<%s, %d, %d>", which ? "bn_bwd_slab_kernel" : "bn_fwd_slab_kernel", dtype == 0 ? "float" : RD_T16_NAME, A, slab_np(pixels));
+  snprintf(buf, sizeof(buf), "%s<%s, %d, %d>", which ? "bn_bwd_slab_kernel" : "bn_fwd_slab_kernel", elem_name(dtype), A, slab_np(pixels));
   return buf;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // Device lambdas that capture register arrays by reference MUST be inlined: an out-of-line closure call forces every captured
 // array into scratch (or LDS via promote-alloca) -- seen as private_segment 48..80 bytes / +16 KB LDS on the conv kernels.
@@ -421,5 +422,33 @@ __device__ __forceinline__ void bn_rows_sum(const float2* __restrict__ p2, int r
   }
   for (; r < rows; r += 256) { const float2 v = p2[(int64_t)r * C + c]; a += (double)v.x; b += (double)v.y; }
 }
+
+// ---- host side: run-time code -> compile-time choice for the launchers ---------------------------------------
+// A launcher writes its launch line once, in terms of T, inside  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; ... });
+// dtype code 0 is float, every other code is this build's 16-bit type (rd_api.cpp has picked the namespace from the code already).
+template <typename T> struct ElemTag { using type = T; };
+template <typename F>
+static inline decltype(auto) with_elem(int dtype, F&& f) {
+  if (dtype == 0) return f(ElemTag<float>{});
+  return f(ElemTag<bf16_t>{});
+}
+template <typename F>
+static inline decltype(auto) with_bool(bool b, F&& f) {
+  if (b) return f(std::true_type{});
+  return f(std::false_type{});
+}
+template <typename F>
+static inline void act_dispatch(int act, F&& f) {   // compile-time activation variants for the streaming kernels
+  switch (act) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, -1>{}); break;
+  }
+}
+static inline int elem_size(int dtype) { return dtype == 0 ? 4 : 2; }                        // bytes per element
+static inline int elem_vec(int dtype) { return dtype == 0 ? 4 : 8; }                         // elements per 16-byte vector (Elem<T>::VE)
+static inline const char* elem_name(int dtype) { return dtype == 0 ? "float" : RD_T16_NAME; }    // T in the instantiation names
 
 }  // namespace rd

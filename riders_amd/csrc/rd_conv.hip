@@ -1165,14 +1165,14 @@ static void conv_tiles(int M, int Cout, int& bn, int& wm) {
 
 // parity-class walk of a stride-2 layer's data gradient (conv_gemm_kernel PAR): whole 128-byte channel stages, one source, no statistics
 static bool conv_gemm_par(const ConvArgs& a, int dtype) {
-  const int bke = STAGE_BYTES / (dtype == 0 ? 4 : 2), Cin = a.C1 + a.C2;
+  const int bke = STAGE_BYTES / elem_size(dtype), Cin = a.C1 + a.C2;
   return rd_opt(OPT_CONV_PAR, 1) != 0 /* A/B switch (rd_set_option) */ && a.dil == 2 && a.stride == 1 && !a.ups && a.C2 == 0 && Cin % bke == 0 && !a.stats && !a.pool2 && a.K == a.KH * a.KW * Cin &&
          a.Kpad == a.K;
 }
 // the implicit-GEMM kernel's instantiation and grid for a descriptor: read by the launcher and by the name query
 struct GemmPlan { int bn, wm; bool vec, deep, par; dim3 grid; };
 static GemmPlan conv_gemm_plan(const ConvArgs& a, int dtype) {
-  const int es = dtype == 0 ? 4 : 2, ve = 16 / es, bke = STAGE_BYTES / es, Cin = a.C1 + a.C2;
+  const int es = elem_size(dtype), ve = 16 / es, bke = STAGE_BYTES / es, Cin = a.C1 + a.C2;
   GemmPlan p;
   conv_tiles(a.M, a.Cout, p.bn, p.wm);
   p.vec = (Cin % ve == 0) && (a.C1 % ve == 0);
@@ -1282,8 +1282,7 @@ static bool conv_skinny_ok(const ConvArgs& a, int dtype) {
 }
 static void launch_linear_skinny(const ConvArgs& a, int dtype, hipStream_t st) {
   const dim3 grid((unsigned)cdiv(a.M, 16), (unsigned)cdiv(a.Cout, 16));
-  if (dtype == 0) hipLaunchKernelGGL((linear_skinny_kernel<float>), grid, dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((linear_skinny_kernel<bf16_t>), grid, dim3(512), 0, st, a);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; hipLaunchKernelGGL((linear_skinny_kernel<T>), grid, dim3(512), 0, st, a); });
 }
 
 // ---- image stems: ONE 16-byte channel vector per input pixel (3 channels zero-padded to 8 bf16 / 4 fp32 by the caller), <= 32 outputs ----------
@@ -1362,7 +1361,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(ConvArgs a, int ntile) {
 }
 static int conv_stem_min_m() { return rd_opt(OPT_CONV_STEM_MIN_M, 65536); }      // test hook: 0 routes small cases here
 static bool conv_stem_ok(const ConvArgs& a, int dtype) {
-  const int ve = dtype == 0 ? 4 : 8, taps = a.KH * a.KW;
+  const int ve = elem_vec(dtype), taps = a.KH * a.KW;
   return a.C1 == ve && a.C2 == 0 && !a.ups && a.dil == 1 && !a.pool2 && !a.in_scale && !a.bn_y && a.KH == a.KW && (taps == 9 || taps == 49) &&
          (a.Cout == 16 || a.Cout == 32) && a.K == taps * ve && a.Kpad >= ((taps + 3) / 4) * 4 * ve && a.M >= conv_stem_min_m() &&
          (int64_t)a.N * a.Hin * a.Win < ((int64_t)1 << 27);
@@ -1371,10 +1370,11 @@ static int conv_stem_blocks(const ConvArgs& a) { return (int)std::min<int64_t>(c
 static void launch_conv_stem(const ConvArgs& a, int dtype, hipStream_t st) {
   const int ntile = (int)cdiv(a.M, 16), taps = a.KH * a.KW;
   const dim3 grid((unsigned)conv_stem_blocks(a));
-#define RD_STEM(TT, NCTV, NSV) hipLaunchKernelGGL((conv_stem_kernel<TT, NCTV, NSV>), grid, dim3(256), 0, st, a, ntile)
-#define RD_STEM_T(TT) { if (a.Cout == 32) { if (taps == 49) RD_STEM(TT, 2, 13); else RD_STEM(TT, 2, 3); } else { if (taps == 49) RD_STEM(TT, 1, 13); else RD_STEM(TT, 1, 3); } }
-  if (dtype == 0) RD_STEM_T(float) else RD_STEM_T(bf16_t)
-#undef RD_STEM_T
+#define RD_STEM(NCTV, NSV) hipLaunchKernelGGL((conv_stem_kernel<T, NCTV, NSV>), grid, dim3(256), 0, st, a, ntile)
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    if (a.Cout == 32) { if (taps == 49) RD_STEM(2, 13); else RD_STEM(2, 3); }
+    else { if (taps == 49) RD_STEM(1, 13); else RD_STEM(1, 3); }
+  });
 #undef RD_STEM
 }
 
@@ -1416,7 +1416,7 @@ void launch_conv(const ConvArgs& a, int dtype, hipStream_t st) {
     case ConvRoute::Pw: launch_conv_pw(a, dtype, st); return;
     case ConvRoute::C1: launch_conv3x3_c1(a, dtype, st); return;
     case ConvRoute::Patch3x3: launch_conv3x3(a, dtype, st); return;
-    case ConvRoute::Gemm: if (dtype == 0) launch_conv_t<float>(a, st); else launch_conv_t<bf16_t>(a, st); return;
+    case ConvRoute::Gemm: with_elem(dtype, [&](auto e) { launch_conv_t<typename decltype(e)::type>(a, st); }); return;
   }
 }
 
@@ -1493,7 +1493,7 @@ const char* conv_kernel_name(const ConvArgs& a, int dtype) {
   }
   static thread_local char buf[96];
   const GemmPlan p = conv_gemm_plan(a, dtype);
-  snprintf(buf, sizeof(buf), "conv_gemm_kernel<%s, %d, %s, %d, %s, %s>", dtype == 0 ? "float" : RD_T16_NAME, p.bn, p.vec ? "true" : "false", p.wm,
+  snprintf(buf, sizeof(buf), "conv_gemm_kernel<%s, %d, %s, %d, %s, %s>", elem_name(dtype), p.bn, p.vec ? "true" : "false", p.wm,
            p.deep ? "true" : "false", p.par ? "true" : "false");
   return buf;
 }
@@ -1504,10 +1504,8 @@ void launch_pack_weights(const float* w, void* out, int Cout, int Cin, int KH, i
   int rows_pad = conv_rows_pad(rows), Kpad = conv_kpad(KH * KW * C, dtype);
   int64_t total = (int64_t)rows_pad * Kpad;
   unsigned grid = (unsigned)std::min<int64_t>(cdiv(total, 256), 4096);
-  if (dtype == 0)
-    hipLaunchKernelGGL((pack_weights_kernel<float>), dim3(grid), dim3(256), 0, st, w, (float*)out, Cout, Cin, KH, KW, mode, rows_pad, Kpad, CinSrc);
-  else
-    hipLaunchKernelGGL((pack_weights_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, w, (bf16_t*)out, Cout, Cin, KH, KW, mode, rows_pad, Kpad, CinSrc);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((pack_weights_kernel<T>), dim3(grid), dim3(256), 0, st, w, (T*)out, Cout, Cin, KH, KW, mode, rows_pad, Kpad, CinSrc); });
 }
 
 // the same with a block map (round 6): block b works on item map[b].x as block map[b].y of map[b].z -- the grid is the SUM of what the items
@@ -1709,12 +1707,12 @@ void launch_wgrad(WgradArgs a, int dtype, float* dw, int accumulate, hipStream_t
     a.nsplit = (int)cdiv(a.M, a.rows_per_split);
   };
   switch (wgrad_route(a, dtype)) {
-    case WgradRoute::Tiny: reduce(dtype == 0 ? launch_wgrad_tiny<float>(a, st) : launch_wgrad_tiny<bf16_t>(a, st)); return;
+    case WgradRoute::Tiny: reduce(with_elem(dtype, [&](auto e) { return launch_wgrad_tiny<typename decltype(e)::type>(a, st); })); return;
     case WgradRoute::Tr3x3: launch_wgrad3x3_tr(a, st); reduce(wgrad3x3_tr_blocks(a)); return;
     case WgradRoute::Halo: {
       int TH, TW; halo_geom(Cin, a.Cout, TH, TW);
       const int nblk = (int)std::min<int64_t>((int64_t)a.N * cdiv(a.OH, TH) * cdiv(a.OW, TW), HALO_BLOCKS);
-      if (dtype == 0) launch_wgrad_halo_t<float>(a, nblk, st); else launch_wgrad_halo_t<bf16_t>(a, nblk, st);
+      with_elem(dtype, [&](auto e) { launch_wgrad_halo_t<typename decltype(e)::type>(a, nblk, st); });
       reduce(nblk);
       return;
     }
@@ -1732,7 +1730,7 @@ void launch_wgrad(WgradArgs a, int dtype, float* dw, int accumulate, hipStream_t
     case WgradRoute::Generic: {
       split(32);
       const bool vec = (Cin % 4 == 0) && (a.C1 % 4 == 0);
-      if (dtype == 0) launch_wgrad_t<float>(a, vec, st); else launch_wgrad_t<bf16_t>(a, vec, st);
+      with_elem(dtype, [&](auto e) { launch_wgrad_t<typename decltype(e)::type>(a, vec, st); });
       reduce(a.nsplit);
       return;
     }

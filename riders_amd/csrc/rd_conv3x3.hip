@@ -627,7 +627,7 @@ static int pick_bn3(int cout) { return cout <= 16 ? 16 : (cout <= 32 ? 32 : (cou
 
 bool conv3x3_ok(const ConvArgs& a, int dtype) {
   const int Cin = a.C1 + a.C2;
-  const int ve = dtype == 0 ? 4 : 8, cke = dtype == 0 ? 32 : 64;
+  const int ve = elem_vec(dtype), cke = dtype == 0 ? 32 : 64;
   if ((int64_t)a.N * a.Hin * a.Win >= (int64_t)1 << 31) return false;   // the kernel keeps source pixel indices in 32 bits
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.OH == a.Hin && a.OW == a.Win && (Cin % cke == 0) &&
          (a.C1 % ve == 0);
@@ -661,8 +661,7 @@ static void launch3_t(const ConvArgs& a, hipStream_t st) {
 #undef RD_C3
 }
 void launch_conv3x3(const ConvArgs& a, int dtype, hipStream_t st) {
-  if (dtype == 0) launch3_t<float>(a, st);
-  else launch3_t<bf16_t>(a, st);
+  with_elem(dtype, [&](auto e) { launch3_t<typename decltype(e)::type>(a, st); });
 }
 
 static bool geom3x3(const ConvArgs& a) {
@@ -670,7 +669,7 @@ static bool geom3x3(const ConvArgs& a) {
 }
 // narrow layers: Cin bytes per pixel in {32, 64} with Cout <= 64, or 128 bytes with Cout <= 16
 bool conv3x3_small_ok(const ConvArgs& a, int dtype) {
-  const int Cin = a.C1 + a.C2, es = dtype == 0 ? 4 : 2, ve = 16 / es;
+  const int Cin = a.C1 + a.C2, es = elem_size(dtype), ve = 16 / es;
   const int cb = Cin * es;
   if (!geom3x3(a) || (cb != 32 && cb != 64 && cb != 128) || (a.C1 % ve) != 0) return false;
   if ((int64_t)a.N * a.Hin * a.Win >= (int64_t)1 << 31) return false;   // the kernel keeps pixel indices in 32 bits
@@ -681,7 +680,7 @@ int conv3x3_small_blocks(const ConvArgs& a, int dtype) {   // persistent blocks 
   const int64_t ntiles = (int64_t)a.N * cdiv(a.OH, w8 ? 16 : 8) * cdiv(a.OW, w8 ? 8 : 16);
   // (test hook, rd_set_option "conv3x3_g8": few persistent blocks -> several tiles per block on small cases)
   // persistent grid = resident capacity: 8 XCDs x 32 CUs x (4 or 2 blocks per CU, see small_min_waves)
-  const int cb_slots = ((a.C1 + a.C2) * (dtype == 0 ? 4 : 2)) / 16;
+  const int cb_slots = ((a.C1 + a.C2) * elem_size(dtype)) / 16;
   const int per_cu = a.d2s ? small_min_waves_d2s() : small_min_waves(cb_slots, pick_bn3(a.Cout));
   return 8 * (int)std::min<int64_t>(cdiv(ntiles, 8), rd_opt(OPT_CONV3X3_G8, 32 * per_cu));
 }
@@ -714,29 +713,28 @@ static void launch_small_t(const ConvArgs& a, hipStream_t st) {
 // instantiation names as rocprofv3 prints them (bench.py groups launches by kernel)
 const char* conv3x3_small_name(const ConvArgs& a, int dtype) {
   static thread_local char buf[96];
-  const int es = dtype == 0 ? 4 : 2;
+  const int es = elem_size(dtype);
   if (a.d2s) snprintf(buf, sizeof(buf), "conv3x3_small_kernel<%s, 4, 64, %s, false, true>", RD_T16_NAME, use_w8(a) ? "true" : "false");
   else
-  snprintf(buf, sizeof(buf), "conv3x3_small_kernel<%s, %d, %d, %s, %s>", dtype == 0 ? "float" : RD_T16_NAME, (a.C1 + a.C2) * es / 16, pick_bn3(a.Cout),
+  snprintf(buf, sizeof(buf), "conv3x3_small_kernel<%s, %d, %d, %s, %s>", elem_name(dtype), (a.C1 + a.C2) * es / 16, pick_bn3(a.Cout),
            use_w8(a) ? "true" : "false", a.in_scale ? "true" : "false");
   return buf;
 }
 const char* conv3x3_patch_name(const ConvArgs& a, int dtype) {
   static thread_local char buf[96];
   const int bn_max = rd_opt(OPT_PATCH_BN_MAX, 64);
-  snprintf(buf, sizeof(buf), "conv3x3_patch_kernel<%s, %d, %s>", dtype == 0 ? "float" : RD_T16_NAME, std::min(bn_max, pick_bn3(a.Cout)),
+  snprintf(buf, sizeof(buf), "conv3x3_patch_kernel<%s, %d, %s>", elem_name(dtype), std::min(bn_max, pick_bn3(a.Cout)),
            use_w8(a) ? "true" : "false");
   return buf;
 }
 void launch_conv3x3_small(const ConvArgs& a, int dtype, hipStream_t st) {
-  if (dtype == 0) launch_small_t<float>(a, st);
-  else launch_small_t<bf16_t>(a, st);
+  with_elem(dtype, [&](auto e) { launch_small_t<typename decltype(e)::type>(a, st); });
 }
 
 static int conv1x1_min_m() { return rd_opt(OPT_CONV1X1_MIN_M, 8192); }   // test hook: 0 forces the kernel
 // 1x1 / stride 1 / single source, K within two k-steps (Cin * sizeof <= 128 bytes), Cin a multiple of the 16-byte vector
 bool conv1x1_direct_ok(const ConvArgs& a, int dtype) {
-  const int es = dtype == 0 ? 4 : 2, ve = 16 / es;
+  const int es = elem_size(dtype), ve = 16 / es;
   return a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.dil == 1 && a.C2 == 0 && !a.ups && a.OH == a.Hin && a.OW == a.Win &&
          (a.C1 % ve) == 0 && a.C1 * es <= 128 && a.M >= conv1x1_min_m();
 }
@@ -744,13 +742,13 @@ int conv1x1_direct_rows(const ConvArgs& a) { return (int)std::min<int64_t>(cdiv(
 void launch_conv1x1_direct(const ConvArgs& a, int dtype, hipStream_t st) {
   // at most 64 output channels per block: the persistent form keeps 2 x 4 x BN/16 statistics registers next to the accumulators and the
   // weight fragments (BN = 128: 232-304 VGPRs, one or two waves per SIMD); the input re-read per channel block is the small operand here
-  const int bn = std::min(64, pick_bn3(a.Cout)), es = dtype == 0 ? 4 : 2;
+  const int bn = std::min(64, pick_bn3(a.Cout)), es = elem_size(dtype);
   const int steps = a.C1 * es <= 64 ? 1 : 2;
   dim3 grid((unsigned)conv1x1_direct_rows(a), (unsigned)cdiv(a.Cout, bn));
-#define RD_P1(TT, BNV, SV) hipLaunchKernelGGL((conv1x1_direct_kernel<TT, BNV, SV>), grid, dim3(256), 0, st, a)
-#define RD_P1B(TT, SV) { if (bn == 16) RD_P1(TT, 16, SV); else if (bn == 32) RD_P1(TT, 32, SV); else RD_P1(TT, 64, SV); }
-  if (dtype == 0) { if (steps == 1) RD_P1B(float, 1) else RD_P1B(float, 2) }
-  else { if (steps == 1) RD_P1B(bf16_t, 1) else RD_P1B(bf16_t, 2) }
+#define RD_P1(BNV, SV) hipLaunchKernelGGL((conv1x1_direct_kernel<T, BNV, SV>), grid, dim3(256), 0, st, a)
+#define RD_P1B(SV) { if (bn == 16) RD_P1(16, SV); else if (bn == 32) RD_P1(32, SV); else RD_P1(64, SV); }
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    if (steps == 1) RD_P1B(1) else RD_P1B(2) });
 #undef RD_P1B
 #undef RD_P1
 }
@@ -890,20 +888,19 @@ bool conv_few_ok(const ConvArgs& a) {
 }
 int conv_few_blocks(const ConvArgs& a) { return (int)std::min<int64_t>(cdiv(a.M, 256 * 4), 2048); }
 void launch_conv_few(const ConvArgs& a, int dtype, hipStream_t st) {
-  if (a.KH == 1 && a.C1 == 1 && a.dil == 1 && !a.stats && !a.add1 && a.Cout % (dtype == 0 ? 4 : 8) == 0 && 256 % (a.Cout / (dtype == 0 ? 4 : 8)) == 0) {
-    const int G = a.Cout / (dtype == 0 ? 4 : 8);
+  if (a.KH == 1 && a.C1 == 1 && a.dil == 1 && !a.stats && !a.add1 && a.Cout % elem_vec(dtype) == 0 && 256 % (a.Cout / elem_vec(dtype)) == 0) {
+    const int G = a.Cout / elem_vec(dtype);
     const dim3 ge((unsigned)std::min<int64_t>(cdiv((int64_t)a.M * G, 256 * 4), 4096));
-    if (dtype == 0) hipLaunchKernelGGL((pointwise_expand_kernel<float>), ge, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((pointwise_expand_kernel<bf16_t>), ge, dim3(256), 0, st, a);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; hipLaunchKernelGGL((pointwise_expand_kernel<T>), ge, dim3(256), 0, st, a); });
     return;
   }
   const dim3 grid((unsigned)conv_few_blocks(a));
-#define RD_FEW(TT) { if (a.dil == 2) hipLaunchKernelGGL((conv_few_kernel<TT, 3, 32, 4, 2>), grid, dim3(256), 0, st, a);        \
-                     else if (a.KH == 3) hipLaunchKernelGGL((conv_few_kernel<TT, 3, 3, 4, 1>), grid, dim3(256), 0, st, a);       \
-                     else if (a.C1 == 1) hipLaunchKernelGGL((conv_few_kernel<TT, 1, 1, 32, 1>), grid, dim3(256), 0, st, a);      \
-                     else hipLaunchKernelGGL((conv_few_kernel<TT, 1, 32, 4, 1>), grid, dim3(256), 0, st, a); }
-  if (dtype == 0) RD_FEW(float) else RD_FEW(bf16_t)
-#undef RD_FEW
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    if (a.dil == 2) hipLaunchKernelGGL((conv_few_kernel<T, 3, 32, 4, 2>), grid, dim3(256), 0, st, a);
+    else if (a.KH == 3) hipLaunchKernelGGL((conv_few_kernel<T, 3, 3, 4, 1>), grid, dim3(256), 0, st, a);
+    else if (a.C1 == 1) hipLaunchKernelGGL((conv_few_kernel<T, 1, 1, 32, 1>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_few_kernel<T, 1, 32, 4, 1>), grid, dim3(256), 0, st, a);
+  });
 }
 
 bool conv3x3_c1_ok(const ConvArgs& a) {
@@ -911,8 +908,7 @@ bool conv3x3_c1_ok(const ConvArgs& a) {
 }
 void launch_conv3x3_c1(const ConvArgs& a, int dtype, hipStream_t st) {
   unsigned grid = (unsigned)std::min<int64_t>(cdiv(a.M, 256), 256 * 32);
-  if (dtype == 0) hipLaunchKernelGGL((conv3x3_c1_kernel<float>), dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((conv3x3_c1_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, a);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; hipLaunchKernelGGL((conv3x3_c1_kernel<T>), dim3(grid), dim3(256), 0, st, a); });
 }
 
 }  // namespace rd

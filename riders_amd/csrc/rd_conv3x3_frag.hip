@@ -571,7 +571,7 @@ static int frag_variant_opt(int id, int dflt, int bn_want) {
 
 static bool frag_plan(const ConvArgs& a, int dtype, FragPlan& p) {
   const int Cin = a.C1 + a.C2;
-  const int ve = dtype == 0 ? 4 : 8, cke = dtype == 0 ? 32 : 64;
+  const int ve = elem_vec(dtype), cke = dtype == 0 ? 32 : 64;
   if (!(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.dil == 1 && a.OH == a.Hin && a.OW == a.Win)) return false;
   if ((Cin % cke) || (a.C1 % ve) || a.Cout <= 16) return false;
   if ((int64_t)a.N * a.Hin * a.Win >= (int64_t)1 << 31) return false;   // the kernel keeps source pixel indices in 32 bits
@@ -642,7 +642,7 @@ const char* conv3x3_frag_name(const ConvArgs& a, int dtype) {
   FragPlan p;
   if (!frag_plan(a, dtype, p)) return "";      // (an out_d2s / in_s2d descriptor this kernel has no plan for: rd_conv_fwd refuses it)
   static const int npt[] = {8, 4, 4, 8, 4, 4, 8}, wpx[] = {1, 2, 2, 2, 4, 4, 4}, wch[] = {4, 4, 2, 2, 2, 1, 1};
-  const bool multi = (a.C1 + a.C2) * (dtype == 0 ? 4 : 2) > STAGE_BYTES;
+  const bool multi = (a.C1 + a.C2) * elem_size(dtype) > STAGE_BYTES;
   if (p.v32) {
     const Frag32Variant& w = kFrag32Variants[p.v32];
     snprintf(buf, sizeof(buf), "conv3x3_frag32_kernel<%s, %d, %d, %d, %d, %s>", RD_T16_NAME, w.nq, w.wpx, w.wch, w.cw, multi ? "true" : "false");
@@ -650,7 +650,7 @@ const char* conv3x3_frag_name(const ConvArgs& a, int dtype) {
   }
   // all nine template arguments, as rocprofv3 prints an instantiation (LIN, MULTI, AFF, D2S, S2D): bench.py matches its per-launch tallies to the
   // kernel trace by this exact string (until round 6 the D2S / S2D defaults were left out and the register-fed family never matched)
-  const char* T16 = dtype == 0 ? "float" : RD_T16_NAME;
+  const char* T16 = elem_name(dtype);
   if (a.s2d) snprintf(buf, sizeof(buf), "conv3x3_frag_kernel<%s, %d, %d, %d, %s, %s, false, false, true>", RD_T16_NAME, npt[p.variant], wpx[p.variant], wch[p.variant],
                       p.lin ? "true" : "false", multi ? "true" : "false");
   else if (a.d2s) snprintf(buf, sizeof(buf), "conv3x3_frag_kernel<%s, %d, %d, %d, %s, %s, false, true, false>", RD_T16_NAME, npt[p.variant], wpx[p.variant], wch[p.variant],
@@ -734,8 +734,7 @@ static void launch_frag_t(const ConvArgs& a, int dtype, hipStream_t st) {
   }
 }
 void launch_conv3x3_frag(const ConvArgs& a, int dtype, hipStream_t st) {
-  if (dtype == 0) launch_frag_t<float>(a, dtype, st);
-  else launch_frag_t<bf16_t>(a, dtype, st);
+  with_elem(dtype, [&](auto e) { launch_frag_t<typename decltype(e)::type>(a, dtype, st); });
 }
 
 }  // namespace rd

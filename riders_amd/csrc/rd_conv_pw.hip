@@ -225,7 +225,7 @@ __global__ __launch_bounds__(64 * KS * NT) void pw_gemm_kernel(ConvArgs a, int m
 static int pw_min_m() { return rd_opt(OPT_PW_MIN_M, -1); }      // test hook (rd_set_option "pw_min_m": 0 forces, 1 << 30 disables)
 // the shape alone (ConvArgs::bn_y / add1 / stats are per call)
 static bool conv_pw_shape(const ConvArgs& a, int dtype) {
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   const bool form = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.dil == 1 && a.C2 == 0 && !a.ups && a.OH == a.Hin && a.OW == a.Win &&
                     a.K == a.C1 && (a.C1 % ve) == 0 && (a.Cout % 8) == 0 && a.D1 == a.Cout && !a.pool2 && !a.d2s && !a.s2d && a.M <= 16384;
   if (!form) return false;
@@ -248,7 +248,7 @@ const char* conv_pw_name(const ConvArgs& a, int dtype) {
   static thread_local char buf[96];
   int ks, nt;
   pw_config(a, dtype, ks, nt);
-  snprintf(buf, sizeof(buf), "pw_gemm_kernel<%s, %d, %d>", dtype == 0 ? "float" : RD_T16_NAME, ks, nt);
+  snprintf(buf, sizeof(buf), "pw_gemm_kernel<%s, %d, %d>", elem_name(dtype), ks, nt);
   return buf;
 }
 void launch_conv_pw(const ConvArgs& a, int dtype, hipStream_t st) {
@@ -256,10 +256,8 @@ void launch_conv_pw(const ConvArgs& a, int dtype, hipStream_t st) {
   pw_config(a, dtype, ks, nt);
   const int mtiles = (int)cdiv(a.M, 64), ngroups = (int)cdiv(a.Cout, 64 * nt);
   const dim3 grid((unsigned)(8 * cdiv(mtiles, 8) * ngroups));
-#define RD_PW(TT, KSV, NTV) hipLaunchKernelGGL((pw_gemm_kernel<TT, KSV, NTV, 2>), grid, dim3(64 * KSV * NTV), 0, st, a, mtiles, ngroups)
-#define RD_PW_T(TT) { if (ks == 8) RD_PW(TT, 8, 1); else if (ks == 4) RD_PW(TT, 4, 1); else RD_PW(TT, 1, 4); }
-  if (dtype == 0) RD_PW_T(float) else RD_PW_T(bf16_t)
-#undef RD_PW_T
+#define RD_PW(KSV, NTV) hipLaunchKernelGGL((pw_gemm_kernel<T, KSV, NTV, 2>), grid, dim3(64 * KSV * NTV), 0, st, a, mtiles, ngroups)
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; if (ks == 8) RD_PW(8, 1); else if (ks == 4) RD_PW(4, 1); else RD_PW(1, 4); });
 #undef RD_PW
 }
 

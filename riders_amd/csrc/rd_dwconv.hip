@@ -614,24 +614,22 @@ int dwconv_stats_rows(int N, int OH, int OW, int C, int k, int s) {
 void launch_dwconv_fwd(const void* x, const float* w, void* y, int N, int H, int W, int C, int OH, int OW, int k, int s, int p, int dtype,
                        hipStream_t st, float* stats) {
   if (dw_quad_ok(C, k, s)) {
-    if (dtype == 0) launch_dw_quad<float, 0>(x, w, y, N, H, W, C, OH, OW, k, s, p, st, stats);
-    else launch_dw_quad<bf16_t, 0>(x, w, y, N, H, W, C, OH, OW, k, s, p, st, stats);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; launch_dw_quad<T, 0>(x, w, y, N, H, W, C, OH, OW, k, s, p, st, stats); });
     return;
   }
   int64_t n = (int64_t)N * OH * OW * C;
-  if (dtype == 0) hipLaunchKernelGGL((dwconv_fwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)x, w, (float*)y, N, H, W, C, OH, OW, k, s, p);
-  else hipLaunchKernelGGL((dwconv_fwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)x, w, (bf16_t*)y, N, H, W, C, OH, OW, k, s, p);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((dwconv_fwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)x, w, (T*)y, N, H, W, C, OH, OW, k, s, p); });
 }
 void launch_dwconv_dgrad(const void* dy, const float* w, void* dx, int N, int H, int W, int C, int OH, int OW, int k, int s, int p,
                          int dtype, hipStream_t st) {
   if (dw_quad_ok(C, k, s)) {
-    if (dtype == 0) launch_dw_quad<float, 1>(dy, w, dx, N, H, W, C, OH, OW, k, s, p, st);
-    else launch_dw_quad<bf16_t, 1>(dy, w, dx, N, H, W, C, OH, OW, k, s, p, st);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; launch_dw_quad<T, 1>(dy, w, dx, N, H, W, C, OH, OW, k, s, p, st); });
     return;
   }
   int64_t n = (int64_t)N * H * W * C;
-  if (dtype == 0) hipLaunchKernelGGL((dwconv_dgrad_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)dy, w, (float*)dx, N, H, W, C, OH, OW, k, s, p);
-  else hipLaunchKernelGGL((dwconv_dgrad_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)dy, w, (bf16_t*)dx, N, H, W, C, OH, OW, k, s, p);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((dwconv_dgrad_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)dy, w, (T*)dx, N, H, W, C, OH, OW, k, s, p); });
 }
 // many depthwise weight gradients finished by ONE launch (item i exactly as dw_wgrad_finalize_tc_kernel: 64 elements x 4 row groups per block)
 struct DwWgradBatch { DwWgradItem it[DW_WGRAD_BATCH_MAX]; };
@@ -690,14 +688,11 @@ void launch_dwconv_wgrad(const void* x, const void* dy, float* partial, float* d
     gx = std::min<int64_t>(gx, std::max<int64_t>(64, (int64_t)N * OH * OW / 32));
     gx = std::max<int64_t>(1, std::min<int64_t>(gx, rows));
     const dim3 grid((unsigned)gx, g.nchunk);
-#define RD_DWG(T, K, S) hipLaunchKernelGGL((dw_wgrad_run_kernel<T, K, S>), grid, dim3(256), 0, st, (const T*)x, (const T*)dy, partial, N, H, W, C, OH, OW, p, g.QB, g.PL)
-    if (dtype == 0) {
-      if (s == 1) { if (k == 3) RD_DWG(float, 3, 1); else RD_DWG(float, 5, 1); }
-      else { if (k == 3) RD_DWG(float, 3, 2); else RD_DWG(float, 5, 2); }
-    } else {
-      if (s == 1) { if (k == 3) RD_DWG(bf16_t, 3, 1); else RD_DWG(bf16_t, 5, 1); }
-      else { if (k == 3) RD_DWG(bf16_t, 3, 2); else RD_DWG(bf16_t, 5, 2); }
-    }
+#define RD_DWG(K, S) hipLaunchKernelGGL((dw_wgrad_run_kernel<T, K, S>), grid, dim3(256), 0, st, (const T*)x, (const T*)dy, partial, N, H, W, C, OH, OW, p, g.QB, g.PL)
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      if (s == 1) { if (k == 3) RD_DWG(3, 1); else RD_DWG(5, 1); }
+      else { if (k == 3) RD_DWG(3, 2); else RD_DWG(5, 2); }
+    });
 #undef RD_DWG
     if (item) { item->rows = (int)gx; return; }
     hipLaunchKernelGGL(dw_wgrad_finalize_tc_kernel, dim3((unsigned)cdiv(C * k * k, 64)), dim3(256), 0, st, partial, (int)gx, C, k * k, dw, accumulate);
@@ -705,17 +700,16 @@ void launch_dwconv_wgrad(const void* x, const void* dy, float* partial, float* d
   }
   RG g = rgeom(C);
   dim3 grid(rows, g.nchunk);
-#define RD_DW(T, KK) hipLaunchKernelGGL((dwconv_wgrad_kernel<T, KK>), grid, dim3(256), 0, st, (const T*)x, (const T*)dy, partial, N, H, W, C, OH, OW, k, s, p, g.CB, g.PL)
-  if (dtype == 0) { if (k <= 3) RD_DW(float, 9); else RD_DW(float, 25); }
-  else { if (k <= 3) RD_DW(bf16_t, 9); else RD_DW(bf16_t, 25); }
+#define RD_DW(KK) hipLaunchKernelGGL((dwconv_wgrad_kernel<T, KK>), grid, dim3(256), 0, st, (const T*)x, (const T*)dy, partial, N, H, W, C, OH, OW, k, s, p, g.CB, g.PL)
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; if (k <= 3) RD_DW(9); else RD_DW(25); });
 #undef RD_DW
   hipLaunchKernelGGL(dwconv_wgrad_finalize_kernel, dim3(C * k * k), dim3(64), 0, st, partial, rows, C * k * k, dw, accumulate);
 }
 void launch_bn_stats(const void* y, float* partial, int64_t pixels, int C, int dtype, hipStream_t st) {
   RG g = rgeom(C);
   dim3 grid(dw_rows(pixels, C), g.nchunk);
-  if (dtype == 0) hipLaunchKernelGGL((bn_stats_kernel<float>), grid, dim3(256), 0, st, (const float*)y, partial, pixels, C, g.CB, g.PL);
-  else hipLaunchKernelGGL((bn_stats_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)y, partial, pixels, C, g.CB, g.PL);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((bn_stats_kernel<T>), grid, dim3(256), 0, st, (const T*)y, partial, pixels, C, g.CB, g.PL); });
 }
 // 16-byte-vector forms (C % VE == 0): one thread interpolates / gathers VE channels
 template <typename T>
@@ -814,37 +808,37 @@ __global__ __launch_bounds__(256) void bilinear_bwd_vec_kernel(const T* __restri
   }
 }
 void launch_bilinear(const void* x, void* y, int N, int H, int W, int C, int OH, int OW, int align, int backward, int dtype, hipStream_t st) {
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   if (C % ve == 0) {
     if (!backward) {
       unsigned g = ew_grid((int64_t)N * OH * OW * (C / ve));
-      if (dtype == 0) hipLaunchKernelGGL((bilinear_fwd_vec_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, OH, OW, align);
-      else hipLaunchKernelGGL((bilinear_fwd_vec_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, N, H, W, C, OH, OW, align);
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+        hipLaunchKernelGGL((bilinear_fwd_vec_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, N, H, W, C, OH, OW, align); });
     } else {
       unsigned g = ew_grid((int64_t)N * H * W * (C / ve));
-      if (dtype == 0) hipLaunchKernelGGL((bilinear_bwd_vec_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, OH, OW, align);
-      else hipLaunchKernelGGL((bilinear_bwd_vec_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, N, H, W, C, OH, OW, align);
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+        hipLaunchKernelGGL((bilinear_bwd_vec_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, N, H, W, C, OH, OW, align); });
     }
     return;
   }
   if (!backward) {
     unsigned g = ew_grid((int64_t)N * OH * OW * C);
-    if (dtype == 0) hipLaunchKernelGGL((bilinear_fwd_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, OH, OW, align);
-    else hipLaunchKernelGGL((bilinear_fwd_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, N, H, W, C, OH, OW, align);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((bilinear_fwd_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, N, H, W, C, OH, OW, align); });
   } else {  // x = dy (N,OH,OW,C), y = dx (N,H,W,C)
     unsigned g = ew_grid((int64_t)N * H * W * C);
-    if (dtype == 0) hipLaunchKernelGGL((bilinear_bwd_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, OH, OW, align);
-    else hipLaunchKernelGGL((bilinear_bwd_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, N, H, W, C, OH, OW, align);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((bilinear_bwd_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, N, H, W, C, OH, OW, align); });
   }
 }
 void launch_sml_head_fwd(const void* out, const float* d, float* pred, int64_t n, float hi, float lo, int dtype, hipStream_t st) {
-  if (dtype == 0) hipLaunchKernelGGL((sml_head_fwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)out, d, pred, n, hi, lo);
-  else hipLaunchKernelGGL((sml_head_fwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)out, d, pred, n, hi, lo);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((sml_head_fwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)out, d, pred, n, hi, lo); });
 }
 void launch_sml_head_bwd(const void* out, const float* d, const float* dpred, void* dout, int64_t n, float hi, float lo, int dtype,
                          hipStream_t st) {
-  if (dtype == 0) hipLaunchKernelGGL((sml_head_bwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)out, d, dpred, (float*)dout, n, hi, lo);
-  else hipLaunchKernelGGL((sml_head_bwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)out, d, dpred, (bf16_t*)dout, n, hi, lo);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((sml_head_bwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)out, d, dpred, (T*)dout, n, hi, lo); });
 }
 void launch_reciprocal(const float* x, const float* dy, float* out, int64_t n, hipStream_t st) {
   hipLaunchKernelGGL(reciprocal_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, dy, out, n);

@@ -200,8 +200,8 @@ __global__ __launch_bounds__(256) void unpad_weight_grad_kernel(const float* __r
 }
 void launch_pad_channels(const void* src, void* dst, int64_t rows, int C, int Cpad, int dtype, hipStream_t st) {
   unsigned g = ew_grid(rows * Cpad);
-  if (dtype == 0) hipLaunchKernelGGL((pad_channels_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)src, (float*)dst, rows, C, Cpad);
-  else hipLaunchKernelGGL((pad_channels_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, rows, C, Cpad);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((pad_channels_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)src, (T*)dst, rows, C, Cpad); });
 }
 void launch_unpad_weight_grad(const float* dwp, float* dw, int Cout, int Cin, int CinPad, int taps, int accumulate, hipStream_t st) {
   hipLaunchKernelGGL(unpad_weight_grad_kernel, dim3((unsigned)cdiv(Cout * Cin * taps, 256)), dim3(256), 0, st, dwp, dw, Cout, Cin, CinPad, taps, accumulate);
@@ -209,68 +209,65 @@ void launch_unpad_weight_grad(const float* dwp, float* dw, int Cout, int Cin, in
 
 void launch_cast(const void* src, void* dst, int64_t n, int sd, int dd, float scale, hipStream_t st) {
   unsigned g = ew_grid(n);
-  if (sd == 0 && dd == 0) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)src, (float*)dst, n, scale);
-  else if (sd == 0 && dd == 1) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), dim3(g), dim3(256), 0, st, (const float*)src, (bf16_t*)dst, n, scale);
-  else if (sd == 1 && dd == 0) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (float*)dst, n, scale);
-  else hipLaunchKernelGGL((cast_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, n, scale);
+  with_elem(sd, [&](auto es) { using S = typename decltype(es)::type;
+    with_elem(dd, [&](auto ed) { using D = typename decltype(ed)::type;
+      hipLaunchKernelGGL((cast_kernel<S, D>), dim3(g), dim3(256), 0, st, (const S*)src, (D*)dst, n, scale); }); });
 }
 void launch_add(const void* a, const void* b, void* out, int64_t n, int dtype, hipStream_t st) {
   if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0) {
-    unsigned g = ew_grid(n / (dtype == 0 ? 4 : 8) + 1);
-    if (dtype == 0) hipLaunchKernelGGL((add_vec_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, n);
-    else hipLaunchKernelGGL((add_vec_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n);
+    unsigned g = ew_grid(n / elem_vec(dtype) + 1);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((add_vec_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)out, n); });
     return;
   }
-  if (dtype == 0) hipLaunchKernelGGL((add_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, n);
-  else hipLaunchKernelGGL((add_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((add_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)out, n); });
 }
 void launch_nchw_to_nhwc(const void* src, void* dst, int N, int C, int H, int W, int sd, int dd, float scale, hipStream_t st) {
   unsigned g = ew_grid((int64_t)N * C * H * W);
-  if (sd == 0 && dd == 0) hipLaunchKernelGGL((nchw_to_nhwc_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)src, (float*)dst, N, C, H, W, scale);
-  else if (sd == 0 && dd == 1) hipLaunchKernelGGL((nchw_to_nhwc_kernel<float, bf16_t>), dim3(g), dim3(256), 0, st, (const float*)src, (bf16_t*)dst, N, C, H, W, scale);
-  else if (sd == 1 && dd == 0) hipLaunchKernelGGL((nchw_to_nhwc_kernel<bf16_t, float>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (float*)dst, N, C, H, W, scale);
-  else hipLaunchKernelGGL((nchw_to_nhwc_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, N, C, H, W, scale);
+  with_elem(sd, [&](auto es) { using S = typename decltype(es)::type;
+    with_elem(dd, [&](auto ed) { using D = typename decltype(ed)::type;
+      hipLaunchKernelGGL((nchw_to_nhwc_kernel<S, D>), dim3(g), dim3(256), 0, st, (const S*)src, (D*)dst, N, C, H, W, scale); }); });
 }
 void launch_nhwc_to_nchw(const void* src, void* dst, int N, int C, int H, int W, int sd, int dd, hipStream_t st) {
   unsigned g = ew_grid((int64_t)N * C * H * W);
-  if (sd == 0 && dd == 0) hipLaunchKernelGGL((nhwc_to_nchw_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)src, (float*)dst, N, C, H, W);
-  else if (sd == 0 && dd == 1) hipLaunchKernelGGL((nhwc_to_nchw_kernel<float, bf16_t>), dim3(g), dim3(256), 0, st, (const float*)src, (bf16_t*)dst, N, C, H, W);
-  else if (sd == 1 && dd == 0) hipLaunchKernelGGL((nhwc_to_nchw_kernel<bf16_t, float>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (float*)dst, N, C, H, W);
-  else hipLaunchKernelGGL((nhwc_to_nchw_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, N, C, H, W);
+  with_elem(sd, [&](auto es) { using S = typename decltype(es)::type;
+    with_elem(dd, [&](auto ed) { using D = typename decltype(ed)::type;
+      hipLaunchKernelGGL((nhwc_to_nchw_kernel<S, D>), dim3(g), dim3(256), 0, st, (const S*)src, (D*)dst, N, C, H, W); }); });
 }
 void launch_transpose_last2(const void* src, void* dst, int64_t B, int R, int Cc, int dtype, hipStream_t st) {
   unsigned g = ew_grid(B * R * Cc);
-  if (dtype == 0) hipLaunchKernelGGL((transpose_last2_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)src, (float*)dst, B, R, Cc);
-  else hipLaunchKernelGGL((transpose_last2_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, R, Cc);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((transpose_last2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)src, (T*)dst, B, R, Cc); });
 }
 void launch_concat2(const void* a, const void* b, void* out, int64_t rows, int Ca, int Cb, int dtype, hipStream_t st) {
   unsigned g = ew_grid(rows * (Ca + Cb));
-  if (dtype == 0) hipLaunchKernelGGL((concat2_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, rows, Ca, Cb);
-  else hipLaunchKernelGGL((concat2_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, rows, Ca, Cb);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((concat2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)out, rows, Ca, Cb); });
 }
 void launch_split2(const void* in, void* a, void* b, int64_t rows, int Ca, int Cb, int dtype, hipStream_t st) {
   unsigned g = ew_grid(rows * (Ca + Cb));
-  if (dtype == 0) hipLaunchKernelGGL((split2_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)in, (float*)a, (float*)b, rows, Ca, Cb);
-  else hipLaunchKernelGGL((split2_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)a, (bf16_t*)b, rows, Ca, Cb);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((split2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)in, (T*)a, (T*)b, rows, Ca, Cb); });
 }
 void launch_upsample_nearest_fwd(const void* x, void* y, int N, int Hs, int Ws, int Hv, int Wv, int C, int dtype, hipStream_t st) {
   float sh = (float)Hs / (float)Hv, sw = (float)Ws / (float)Wv;
   unsigned g = ew_grid((int64_t)N * Hv * Wv * C);
-  if (dtype == 0) hipLaunchKernelGGL((upsample_nearest_fwd_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)x, (float*)y, N, Hs, Ws, Hv, Wv, C, sh, sw);
-  else hipLaunchKernelGGL((upsample_nearest_fwd_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, N, Hs, Ws, Hv, Wv, C, sh, sw);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((upsample_nearest_fwd_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, N, Hs, Ws, Hv, Wv, C, sh, sw); });
 }
 void launch_upsample_nearest_bwd(const void* dy, void* dx, int N, int Hs, int Ws, int Hv, int Wv, int C, int dtype, hipStream_t st) {
   float sh = (float)Hs / (float)Hv, sw = (float)Ws / (float)Wv;
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   if (C % ve == 0) {
     unsigned gv = ew_grid((int64_t)N * Hs * Ws * (C / ve));
-    if (dtype == 0) hipLaunchKernelGGL((upsample_nearest_bwd_vec_kernel<float>), dim3(gv), dim3(256), 0, st, (const float*)dy, (float*)dx, N, Hs, Ws, Hv, Wv, C, sh, sw);
-    else hipLaunchKernelGGL((upsample_nearest_bwd_vec_kernel<bf16_t>), dim3(gv), dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)dx, N, Hs, Ws, Hv, Wv, C, sh, sw);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((upsample_nearest_bwd_vec_kernel<T>), dim3(gv), dim3(256), 0, st, (const T*)dy, (T*)dx, N, Hs, Ws, Hv, Wv, C, sh, sw); });
     return;
   }
   unsigned g = ew_grid((int64_t)N * Hs * Ws * C);
-  if (dtype == 0) hipLaunchKernelGGL((upsample_nearest_bwd_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)dy, (float*)dx, N, Hs, Ws, Hv, Wv, C, sh, sw);
-  else hipLaunchKernelGGL((upsample_nearest_bwd_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)dx, N, Hs, Ws, Hv, Wv, C, sh, sw);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((upsample_nearest_bwd_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)dy, (T*)dx, N, Hs, Ws, Hv, Wv, C, sh, sw); });
 }
 
 }  // namespace rd

@@ -479,8 +479,8 @@ void launch_bn_head_fwd(const void* y, const float* scale, const float* shift, i
   const size_t lds = (size_t)(p.th + 2) * (p.tw + 2) * 9 * sizeof(float);
   head_dispatch(act, slope, head_cpi(0), [&](auto ac, auto cp) {
     constexpr int A = decltype(ac)::value, CPI = decltype(cp)::value;
-    if (dtype == 0) hipLaunchKernelGGL((bn_head_fwd_kernel<float, A, CPI>), dim3(grid), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((bn_head_fwd_kernel<bf16_t, A, CPI>), dim3(grid), dim3(256), lds, st, a);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((bn_head_fwd_kernel<T, A, CPI>), dim3(grid), dim3(256), lds, st, a); });
   });
 }
 void launch_bn_head_bwd_reduce(const void* dl, const void* y, const float* mean, const float* rstd, const float* scale, const float* shift, int act,
@@ -493,8 +493,8 @@ void launch_bn_head_bwd_reduce(const void* dl, const void* y, const float* mean,
   const size_t lds = std::max((size_t)(p.th + 2) * (p.tw + 2), (size_t)4 * HC * 11) * sizeof(float);
   head_dispatch(act, slope, head_cpi(1), [&](auto ac, auto cp) {
     constexpr int A = decltype(ac)::value, CPI = decltype(cp)::value;
-    if (dtype == 0) hipLaunchKernelGGL((bn_head_bwd_reduce_kernel<float, A, CPI>), dim3(grid), dim3(256), lds, st, a, ntiles);
-    else hipLaunchKernelGGL((bn_head_bwd_reduce_kernel<bf16_t, A, CPI>), dim3(grid), dim3(256), lds, st, a, ntiles);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((bn_head_bwd_reduce_kernel<T, A, CPI>), dim3(grid), dim3(256), lds, st, a, ntiles); });
   });
 }
 void launch_bn_head_bwd_apply(const void* dl, const void* y, const float* mean, const float* rstd, const float* scale, const float* shift, int act,
@@ -509,14 +509,13 @@ void launch_bn_head_bwd_apply(const void* dl, const void* y, const float* mean, 
   const size_t lds = (size_t)(p.th + 2) * (p.tw + 2) * sizeof(float);
   head_dispatch(act, slope, head_cpi(2), [&](auto ac, auto cp) {
     constexpr int A = decltype(ac)::value, CPI = decltype(cp)::value;
-    if (dtype == 0) hipLaunchKernelGGL((bn_head_bwd_apply_kernel<float, A, CPI>), dim3(grid), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((bn_head_bwd_apply_kernel<bf16_t, A, CPI>), dim3(grid), dim3(256), lds, st, a);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; hipLaunchKernelGGL((bn_head_bwd_apply_kernel<T, A, CPI>), dim3(grid), dim3(256), lds, st, a); });
   });
 }
 const char* bn_head_kernel_name(int which, int dtype, int act) {
   static thread_local char buf[96];
   static const char* const names[3] = {"bn_head_fwd_kernel", "bn_head_bwd_reduce_kernel", "bn_head_bwd_apply_kernel"};
-  snprintf(buf, sizeof(buf), "%s<%s, %d, %d>", names[which], dtype == 0 ? "float" : RD_T16_NAME, act == ACT_LRELU ? ACT_LRELU : -1, head_cpi(which));
+  snprintf(buf, sizeof(buf), "%s<%s, %d, %d>", names[which], elem_name(dtype), act == ACT_LRELU ? ACT_LRELU : -1, head_cpi(which));
   return buf;
 }
 

@@ -187,8 +187,8 @@ void launch_frame_thresholds(const void* crops, const float* points, const int* 
   const int S = frame_rmax_splits(R);
   const int vec_ok = ((uintptr_t)crops & 15) == 0;
   if (R > 0) {
-    if (dtype == 0) hipLaunchKernelGGL((frame_rmax_kernel<float>), dim3(R, S), dim3(256), 0, st, (const float*)crops, points, ws, PH, PW, H, W, vec_ok);
-    else hipLaunchKernelGGL((frame_rmax_kernel<bf16_t>), dim3(R, S), dim3(256), 0, st, (const bf16_t*)crops, points, ws, PH, PW, H, W, vec_ok);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((frame_rmax_kernel<T>), dim3(R, S), dim3(256), 0, st, (const T*)crops, points, ws, PH, PW, H, W, vec_ok); });
   }
   hipLaunchKernelGGL(frame_thresholds_kernel, dim3(F), dim3(64), 0, st, ws, frame_start, S, start, step, rmax, thr, retries, flag);
 }
@@ -196,8 +196,8 @@ void launch_frame_thresholds(const void* crops, const float* points, const int* 
 void launch_scatter_crops_frames(const void* crops, const float* points, const int* frame_start, const float* thr, float* depth, float* response,
                                  int F, int PH, int PW, int H, int W, int dtype, hipStream_t st) {
   const dim3 grid((unsigned)cdiv(W, SF_TW), (unsigned)cdiv(H, SF_TH), (unsigned)F);
-  if (dtype == 0) hipLaunchKernelGGL((scatter_frames_kernel<float>), grid, dim3(256), 0, st, (const float*)crops, points, frame_start, thr, depth, response, PH, PW, H, W);
-  else hipLaunchKernelGGL((scatter_frames_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)crops, points, frame_start, thr, depth, response, PH, PW, H, W);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((scatter_frames_kernel<T>), grid, dim3(256), 0, st, (const T*)crops, points, frame_start, thr, depth, response, PH, PW, H, W); });
 }
 
 }  // namespace rd

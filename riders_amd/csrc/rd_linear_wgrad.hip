@@ -260,8 +260,8 @@ void launch_linear_wgrad_batch(const LwgGemm* gemms, int n_gemm, const LwgReduce
       maxb = std::max(maxb, lwg_blocks_per_split(g.C1 + g.C2, g.Cout) * g.nsplit);
     }
     for (int i = n; i < LWG_MAX_ITEMS; i++) b.it[i] = b.it[0];
-    if (dtype == 0) hipLaunchKernelGGL((linear_wgrad_kernel<float>), dim3((unsigned)maxb, (unsigned)n), dim3(256), 0, st, b);
-    else hipLaunchKernelGGL((linear_wgrad_kernel<bf16_t>), dim3((unsigned)maxb, (unsigned)n), dim3(256), 0, st, b);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((linear_wgrad_kernel<T>), dim3((unsigned)maxb, (unsigned)n), dim3(256), 0, st, b); });
   }
   for (int base = 0; base < n_red; base += LWG_MAX_REDS) {
     const int n = std::min(LWG_MAX_REDS, n_red - base);

@@ -584,14 +584,14 @@ __global__ __launch_bounds__(LNT) void loftr_layer_bwd_kernel(const T* __restric
 void launch_loftr_layer_fwd(const void* x, const void* src, const LoftrW& w, void* out, const LoftrSaved& sv, int N, int L, int S,
                             float eps_attn, float eps_ln, int dtype, hipStream_t st) {
   if (N <= 0) return;
-  if (dtype == 0) hipLaunchKernelGGL((loftr_layer_fwd_kernel<float>), dim3((unsigned)N), dim3(LNT), 0, st, (const float*)x, (const float*)src, w, (float*)out, sv, L, S, eps_attn, eps_ln);
-  else hipLaunchKernelGGL((loftr_layer_fwd_kernel<bf16_t>), dim3((unsigned)N), dim3(LNT), 0, st, (const bf16_t*)x, (const bf16_t*)src, w, (bf16_t*)out, sv, L, S, eps_attn, eps_ln);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((loftr_layer_fwd_kernel<T>), dim3((unsigned)N), dim3(LNT), 0, st, (const T*)x, (const T*)src, w, (T*)out, sv, L, S, eps_attn, eps_ln); });
 }
 void launch_loftr_layer_bwd(const void* x, const void* src, const LoftrW& w, const LoftrSaved& sv, const LoftrGrads& gr, int N, int L,
                             int S, float eps_attn, int dtype, hipStream_t st) {
   if (N <= 0) return;
-  if (dtype == 0) hipLaunchKernelGGL((loftr_layer_bwd_kernel<float>), dim3((unsigned)N), dim3(LNT), 0, st, (const float*)x, (const float*)src, w, sv, gr, L, S, eps_attn);
-  else hipLaunchKernelGGL((loftr_layer_bwd_kernel<bf16_t>), dim3((unsigned)N), dim3(LNT), 0, st, (const bf16_t*)x, (const bf16_t*)src, w, sv, gr, L, S, eps_attn);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((loftr_layer_bwd_kernel<T>), dim3((unsigned)N), dim3(LNT), 0, st, (const T*)x, (const T*)src, w, sv, gr, L, S, eps_attn); });
   // LayerNorm parameter gradients: ordered sum of the per-ROI partials
   if (gr.defer_ln) return;      // the caller finishes them later (rd_ln_grad_batch: one launch for every layer application of a stage)
   launch_bn_bwd_finalize(gr.lnp1, N, LC, 1.0, gr.dg1, gr.db1, gr.accumulate, nullptr, nullptr, st);

@@ -173,24 +173,24 @@ int bce_rows(int64_t n) { return (int)ew_grid(n, 1024); }
 void launch_bce_fwd(const void* logits, const float* label, const float* valid, float pw, float* partial, float* loss,
                     float* sums, int64_t n, int dtype, hipStream_t st) {
   int rows = bce_rows(n);
-  if (dtype == 0) hipLaunchKernelGGL((bce_fwd_kernel<float>), dim3(rows), dim3(256), 0, st, (const float*)logits, label, valid, pw, partial, n);
-  else hipLaunchKernelGGL((bce_fwd_kernel<bf16_t>), dim3(rows), dim3(256), 0, st, (const bf16_t*)logits, label, valid, pw, partial, n);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((bce_fwd_kernel<T>), dim3(rows), dim3(256), 0, st, (const T*)logits, label, valid, pw, partial, n); });
   hipLaunchKernelGGL(bce_finalize_kernel, dim3(1), dim3(64), 0, st, partial, rows, loss, sums);
 }
 void launch_bce_bwd(const void* logits, const float* label, const float* valid, float pw, const float* sums, const float* dloss,
                     void* dlogits, int64_t n, int dtype, hipStream_t st) {
-  if (dtype == 0) hipLaunchKernelGGL((bce_bwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)logits, label, valid, pw, sums, dloss, (float*)dlogits, n);
-  else hipLaunchKernelGGL((bce_bwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)logits, label, valid, pw, sums, dloss, (bf16_t*)dlogits, n);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((bce_bwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)logits, label, valid, pw, sums, dloss, (T*)dlogits, n); });
 }
 void launch_sigmoid(const void* x, void* y, int64_t n, int dtype, hipStream_t st) {
-  if (dtype == 0) hipLaunchKernelGGL((sigmoid_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)x, (float*)y, n);
-  else hipLaunchKernelGGL((sigmoid_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, n);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((sigmoid_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)x, (T*)y, n); });
 }
 void launch_scatter_crops(const void* crops, const float* points, float* depth, float* response, int Ncrop, int PH, int PW, int H,
                           int W, float thr, int dtype, hipStream_t st) {
   unsigned g = ew_grid((int64_t)H * W);
-  if (dtype == 0) hipLaunchKernelGGL((scatter_crops_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)crops, points, depth, response, Ncrop, PH, PW, H, W, thr);
-  else hipLaunchKernelGGL((scatter_crops_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)crops, points, depth, response, Ncrop, PH, PW, H, W, thr);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((scatter_crops_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)crops, points, depth, response, Ncrop, PH, PW, H, W, thr); });
 }
 
 }  // namespace rd

@@ -606,21 +606,11 @@ __global__ __launch_bounds__(256) void col_reduce_gen_kernel(const T* __restrict
   }
 }
 static bool gen_ok(int C, int dtype) {
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   return (C % ve) == 0 && C / ve <= 256;
 }
-template <typename F>
-static void act_dispatch(int act, F&& f) {   // compile-time activation variants for the streaming kernels
-  switch (act) {
-    case 0: f(std::integral_constant<int, 0>{}); break;
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    default: f(std::integral_constant<int, -1>{}); break;
-  }
-}
 static bool vec_ok(int C, int dtype) {
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   if (C % ve) return false;
   const int vp = C / ve;
   return vp <= 256 && (256 % vp) == 0;
@@ -724,35 +714,32 @@ void launch_affine_act(const void* y, const float* scale, const float* shift, co
                        int C, int act, float slope, int dtype, hipStream_t st) {
   int64_t total = pixels * C;
   if (vec_ok(C, dtype)) {
-    const int64_t nvec = total / (dtype == 0 ? 4 : 8);
+    const int64_t nvec = total / elem_vec(dtype);
     unsigned gv = ew_grid_per(nvec, 4);
     act_dispatch(act, [&](auto ac) {
       constexpr int A = decltype(ac)::value;
-      if (dtype == 0) { if (res) hipLaunchKernelGGL((affine_act_vec_kernel<float, A, true>), dim3(gv), dim3(256), 0, st, (const float*)y, scale, shift, (const float*)res, (float*)out, nvec, C, act, slope);
-                        else hipLaunchKernelGGL((affine_act_vec_kernel<float, A, false>), dim3(gv), dim3(256), 0, st, (const float*)y, scale, shift, (const float*)res, (float*)out, nvec, C, act, slope); }
-      else { if (res) hipLaunchKernelGGL((affine_act_vec_kernel<bf16_t, A, true>), dim3(gv), dim3(256), 0, st, (const bf16_t*)y, scale, shift, (const bf16_t*)res, (bf16_t*)out, nvec, C, act, slope);
-             else hipLaunchKernelGGL((affine_act_vec_kernel<bf16_t, A, false>), dim3(gv), dim3(256), 0, st, (const bf16_t*)y, scale, shift, (const bf16_t*)res, (bf16_t*)out, nvec, C, act, slope); }
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+        with_bool(res != nullptr, [&](auto r) {
+          hipLaunchKernelGGL((affine_act_vec_kernel<T, A, decltype(r)::value>), dim3(gv), dim3(256), 0, st, (const T*)y, scale, shift, (const T*)res, (T*)out, nvec, C, act, slope); }); });
     });
     return;
   }
   if (gen_ok(C, dtype)) {
-    const int ppb = 256 / (C / (dtype == 0 ? 4 : 8));
+    const int ppb = 256 / (C / elem_vec(dtype));
     unsigned gg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(pixels, gen_ppt() * ppb), 2048));      // >= two pixels per thread (one iteration of the two-pixel loop)
     act_dispatch(act, [&](auto ac) {
       constexpr int A = decltype(ac)::value;
-      if (dtype == 0) { if (res) hipLaunchKernelGGL((affine_act_gen_kernel<float, A, true>), dim3(gg), dim3(256), 0, st, (const float*)y, scale, shift, (const float*)res, (float*)out, pixels, C, act, slope);
-                        else hipLaunchKernelGGL((affine_act_gen_kernel<float, A, false>), dim3(gg), dim3(256), 0, st, (const float*)y, scale, shift, (const float*)res, (float*)out, pixels, C, act, slope); }
-      else { if (res) hipLaunchKernelGGL((affine_act_gen_kernel<bf16_t, A, true>), dim3(gg), dim3(256), 0, st, (const bf16_t*)y, scale, shift, (const bf16_t*)res, (bf16_t*)out, pixels, C, act, slope);
-             else hipLaunchKernelGGL((affine_act_gen_kernel<bf16_t, A, false>), dim3(gg), dim3(256), 0, st, (const bf16_t*)y, scale, shift, (const bf16_t*)res, (bf16_t*)out, pixels, C, act, slope); }
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+        with_bool(res != nullptr, [&](auto r) {
+          hipLaunchKernelGGL((affine_act_gen_kernel<T, A, decltype(r)::value>), dim3(gg), dim3(256), 0, st, (const T*)y, scale, shift, (const T*)res, (T*)out, pixels, C, act, slope); }); });
     });
     return;
   }
   bool v4 = (C % 4 == 0);
   unsigned g = ew_grid(v4 ? total / 4 : total);
-#define RD_AA(T, V) hipLaunchKernelGGL((affine_act_kernel<T, V>), dim3(g), dim3(256), 0, st, (const T*)y, scale, shift, (const T*)res, (T*)out, total, C, act, slope)
-  if (dtype == 0) { if (v4) RD_AA(float, true); else RD_AA(float, false); }
-  else { if (v4) RD_AA(bf16_t, true); else RD_AA(bf16_t, false); }
-#undef RD_AA
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    with_bool(v4, [&](auto v) {
+      hipLaunchKernelGGL((affine_act_kernel<T, decltype(v)::value>), dim3(g), dim3(256), 0, st, (const T*)y, scale, shift, (const T*)res, (T*)out, total, C, act, slope); }); });
 }
 
 bool affine_act_add_ok(int C, int dtype) { return vec_ok(C, dtype); }
@@ -760,12 +747,12 @@ bool affine_act_add_ok(int C, int dtype) { return vec_ok(C, dtype); }
 bool bn_bwd_recomputes(int C, int dtype) { return vec_ok(C, dtype) || gen_ok(C, dtype); }
 void launch_affine_act_add(const void* y, const float* scale, const float* shift, int act1, float slope1, const void* res, void* out,
                            int64_t pixels, int C, int act2, float slope2, int dtype, hipStream_t st) {
-  const int64_t nvec = pixels * C / (dtype == 0 ? 4 : 8);
+  const int64_t nvec = pixels * C / elem_vec(dtype);
   const unsigned gv = ew_grid(nvec);
   act_dispatch(act1 == act2 ? act1 : -1, [&](auto ac) {      // (residual blocks use one activation for both)
     constexpr int A = decltype(ac)::value;
-    if (dtype == 0) hipLaunchKernelGGL((affine_act_add_vec_kernel<float, A, A>), dim3(gv), dim3(256), 0, st, (const float*)y, scale, shift, (const float*)res, (float*)out, nvec, C, act1, slope1, act2, slope2);
-    else hipLaunchKernelGGL((affine_act_add_vec_kernel<bf16_t, A, A>), dim3(gv), dim3(256), 0, st, (const bf16_t*)y, scale, shift, (const bf16_t*)res, (bf16_t*)out, nvec, C, act1, slope1, act2, slope2);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((affine_act_add_vec_kernel<T, A, A>), dim3(gv), dim3(256), 0, st, (const T*)y, scale, shift, (const T*)res, (T*)out, nvec, C, act1, slope1, act2, slope2); });
   });
 }
 
@@ -774,7 +761,7 @@ void launch_affine_act_add(const void* y, const float* scale, const float* shift
 // 3 = the frozen (running-statistics) backward
 const char* bn_kernel_name(int which, int C, int dtype, int act, int flag) {
   static thread_local char buf[96];
-  const char* T = dtype == 0 ? "float" : RD_T16_NAME;
+  const char* T = elem_name(dtype);
   const bool v = vec_ok(C, dtype), g = !v && gen_ok(C, dtype);
   const char* form = v ? "vec" : "gen";
   const int A = (act >= 0 && act <= 3) ? act : -1;
@@ -809,23 +796,25 @@ void launch_bn_bwd_reduce(const void* dz, const void* z, const void* y, const fl
   if (vec_ok(C, dtype)) {
     act_dispatch(act, [&](auto ac) {
       constexpr int A = decltype(ac)::value; (void)A;
-      if (dtype == 0) { if (shift) hipLaunchKernelGGL((col_reduce_vec_kernel<float, 0, true, A>), dim3(grid.x), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); else hipLaunchKernelGGL((col_reduce_vec_kernel<float, 0, false, -1>), dim3(grid.x), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); }
-      else { if (shift) hipLaunchKernelGGL((col_reduce_vec_kernel<bf16_t, 0, true, A>), dim3(grid.x), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); else hipLaunchKernelGGL((col_reduce_vec_kernel<bf16_t, 0, false, -1>), dim3(grid.x), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); }
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;      // without shift the activation's argument is not recomputed: one <T, 0, false, -1> form, whatever A
+        if (shift) hipLaunchKernelGGL((col_reduce_vec_kernel<T, 0, true, A>), dim3(grid.x), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift);
+        else hipLaunchKernelGGL((col_reduce_vec_kernel<T, 0, false, -1>), dim3(grid.x), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift);
+      });
     });
     return;
   }
   if (gen_ok(C, dtype)) {
     act_dispatch(act, [&](auto ac) {
       constexpr int A = decltype(ac)::value; (void)A;
-      if (dtype == 0) { if (shift) hipLaunchKernelGGL((col_reduce_gen_kernel<float, 0, true, A>), dim3(grid.x), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); else hipLaunchKernelGGL((col_reduce_gen_kernel<float, 0, false, -1>), dim3(grid.x), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); }
-      else { if (shift) hipLaunchKernelGGL((col_reduce_gen_kernel<bf16_t, 0, true, A>), dim3(grid.x), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); else hipLaunchKernelGGL((col_reduce_gen_kernel<bf16_t, 0, false, -1>), dim3(grid.x), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift); }
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;      // without shift the activation's argument is not recomputed: one <T, 0, false, -1> form, whatever A
+        if (shift) hipLaunchKernelGGL((col_reduce_gen_kernel<T, 0, true, A>), dim3(grid.x), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift);
+        else hipLaunchKernelGGL((col_reduce_gen_kernel<T, 0, false, -1>), dim3(grid.x), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, partial, pixels, C, act, slope, scale, shift);
+      });
     });
     return;
   }
-  if (dtype == 0)
-    hipLaunchKernelGGL((col_reduce_kernel<float, 0>), grid, dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, partial, pixels, C, g.CB, g.PL, act, slope);
-  else
-    hipLaunchKernelGGL((col_reduce_kernel<bf16_t, 0>), grid, dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, partial, pixels, C, g.CB, g.PL, act, slope);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((col_reduce_kernel<T, 0>), grid, dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, partial, pixels, C, g.CB, g.PL, act, slope); });
 }
 
 void launch_bn_bwd_finalize(const float* partial, int rows, int C, double count, float* dgamma, float* dbeta,
@@ -840,31 +829,34 @@ void launch_bn_bwd_apply(const void* dz, const void* z, const void* y, const flo
   if (!(vec_ok(C, dtype) || gen_ok(C, dtype))) shift = nullptr;
   int64_t total = pixels * C;
   if (vec_ok(C, dtype)) {
-    const int64_t nvec = total / (dtype == 0 ? 4 : 8);
+    const int64_t nvec = total / elem_vec(dtype);
     unsigned gv = ew_grid_per(nvec, 2);
     act_dispatch(act, [&](auto ac) {
       constexpr int A = decltype(ac)::value; (void)A;
-      if (dtype == 0) { if (shift) hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<float, true, A>), dim3(gv), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, scale, c1, c2, shift, (float*)dy, (float*)dres, nvec, C, act, slope); else hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<float, false, -1>), dim3(gv), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, scale, c1, c2, shift, (float*)dy, (float*)dres, nvec, C, act, slope); }
-      else { if (shift) hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<bf16_t, true, A>), dim3(gv), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, scale, c1, c2, shift, (bf16_t*)dy, (bf16_t*)dres, nvec, C, act, slope); else hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<bf16_t, false, -1>), dim3(gv), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, scale, c1, c2, shift, (bf16_t*)dy, (bf16_t*)dres, nvec, C, act, slope); }
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;      // as in launch_bn_bwd_reduce: one <T, false, -1> form without shift
+        if (shift) hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<T, true, A>), dim3(gv), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, c1, c2, shift, (T*)dy, (T*)dres, nvec, C, act, slope);
+        else hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<T, false, -1>), dim3(gv), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, c1, c2, shift, (T*)dy, (T*)dres, nvec, C, act, slope);
+      });
     });
     return;
   }
   if (gen_ok(C, dtype)) {
-    const int ppb = 256 / (C / (dtype == 0 ? 4 : 8));
+    const int ppb = 256 / (C / elem_vec(dtype));
     unsigned gg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(pixels, 2 * ppb), 2048));      // two pixels per thread per iteration (4 / 8: 1244 / 1241 vs 1246 img/s on the SML step)
     act_dispatch(act, [&](auto ac) {
       constexpr int A = decltype(ac)::value; (void)A;
-      if (dtype == 0) { if (shift) hipLaunchKernelGGL((bn_bwd_apply_gen_kernel<float, true, A>), dim3(gg), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, scale, c1, c2, shift, (float*)dy, (float*)dres, pixels, C, act, slope); else hipLaunchKernelGGL((bn_bwd_apply_gen_kernel<float, false, -1>), dim3(gg), dim3(256), 0, st, (const float*)dz, (const float*)z, (const float*)y, mean, rstd, scale, c1, c2, shift, (float*)dy, (float*)dres, pixels, C, act, slope); }
-      else { if (shift) hipLaunchKernelGGL((bn_bwd_apply_gen_kernel<bf16_t, true, A>), dim3(gg), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, scale, c1, c2, shift, (bf16_t*)dy, (bf16_t*)dres, pixels, C, act, slope); else hipLaunchKernelGGL((bn_bwd_apply_gen_kernel<bf16_t, false, -1>), dim3(gg), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, rstd, scale, c1, c2, shift, (bf16_t*)dy, (bf16_t*)dres, pixels, C, act, slope); }
+      with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;      // as in launch_bn_bwd_reduce: one <T, false, -1> form without shift
+        if (shift) hipLaunchKernelGGL((bn_bwd_apply_gen_kernel<T, true, A>), dim3(gg), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, c1, c2, shift, (T*)dy, (T*)dres, pixels, C, act, slope);
+        else hipLaunchKernelGGL((bn_bwd_apply_gen_kernel<T, false, -1>), dim3(gg), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, c1, c2, shift, (T*)dy, (T*)dres, pixels, C, act, slope);
+      });
     });
     return;
   }
   bool v4 = (C % 4 == 0);
   unsigned g = ew_grid(v4 ? total / 4 : total);
-#define RD_BA(T, V) hipLaunchKernelGGL((bn_bwd_apply_kernel<T, V>), dim3(g), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, c1, c2, (T*)dy, (T*)dres, total, C, act, slope)
-  if (dtype == 0) { if (v4) RD_BA(float, true); else RD_BA(float, false); }
-  else { if (v4) RD_BA(bf16_t, true); else RD_BA(bf16_t, false); }
-#undef RD_BA
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    with_bool(v4, [&](auto v) {
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, decltype(v)::value>), dim3(g), dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, c1, c2, (T*)dy, (T*)dres, total, C, act, slope); }); });
 }
 
 // ---- backward through a BatchNorm that normalises with its running statistics (frozen / eval mode).  mean and rstd are constants of the
@@ -1081,11 +1073,12 @@ void launch_bn_frozen_bwd(const void* dz, const void* z, const void* y, const fl
                           const float* shift, float* partial, void* dy, void* dres, int64_t pixels, int C, int act, float slope, int dtype,
                           hipStream_t st) {
   const bool sums = partial != nullptr, fromz = dres != nullptr;
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   const int rows = red_rows(pixels, C);
-#define RD_FZ(K, T, S, Z, GRID, ...) hipLaunchKernelGGL((K<T, S, Z, ##__VA_ARGS__>), GRID, dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, shift, partial, (T*)dy, (T*)dres, pixels, C, RD_FZ_TAIL)
-#define RD_FZ4(K, T, GRID, ...) do { if (sums) { if (fromz) RD_FZ(K, T, true, true, GRID, ##__VA_ARGS__); else RD_FZ(K, T, true, false, GRID, ##__VA_ARGS__); } \
-                                     else { if (fromz) RD_FZ(K, T, false, true, GRID, ##__VA_ARGS__); else RD_FZ(K, T, false, false, GRID, ##__VA_ARGS__); } } while (0)
+  // both macros are used inside with_elem: T is the element type there
+#define RD_FZ(K, S, Z, GRID, ...) hipLaunchKernelGGL((K<T, S, Z, ##__VA_ARGS__>), GRID, dim3(256), 0, st, (const T*)dz, (const T*)z, (const T*)y, mean, rstd, scale, shift, partial, (T*)dy, (T*)dres, pixels, C, RD_FZ_TAIL)
+#define RD_FZ4(K, GRID, ...) do { if (sums) { if (fromz) RD_FZ(K, true, true, GRID, ##__VA_ARGS__); else RD_FZ(K, true, false, GRID, ##__VA_ARGS__); } \
+                                  else { if (fromz) RD_FZ(K, false, true, GRID, ##__VA_ARGS__); else RD_FZ(K, false, false, GRID, ##__VA_ARGS__); } } while (0)
   if (vec_ok(C, dtype) || gen_ok(C, dtype)) {
     const bool v = vec_ok(C, dtype);
     const int ppb = 256 / (C / ve);
@@ -1095,8 +1088,8 @@ void launch_bn_frozen_bwd(const void* dz, const void* z, const void* y, const fl
 #define RD_FZ_TAIL act, slope
     act_dispatch(act, [&](auto ac) {
       constexpr int A = decltype(ac)::value;
-      if (v) { if (dtype == 0) RD_FZ4(bn_frozen_bwd_vec_kernel, float, grid, A); else RD_FZ4(bn_frozen_bwd_vec_kernel, bf16_t, grid, A); }
-      else { if (dtype == 0) RD_FZ4(bn_frozen_bwd_gen_kernel, float, grid, A); else RD_FZ4(bn_frozen_bwd_gen_kernel, bf16_t, grid, A); }
+      if (v) with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; RD_FZ4(bn_frozen_bwd_vec_kernel, grid, A); });
+      else with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; RD_FZ4(bn_frozen_bwd_gen_kernel, grid, A); });
     });
 #undef RD_FZ_TAIL
     return;
@@ -1104,15 +1097,15 @@ void launch_bn_frozen_bwd(const void* dz, const void* z, const void* y, const fl
   RedGeom g = red_geom(C);
   const dim3 grid(rows, g.nchunk);
 #define RD_FZ_TAIL g.CB, g.PL, act, slope
-  if (dtype == 0) RD_FZ4(bn_frozen_bwd_kernel, float, grid); else RD_FZ4(bn_frozen_bwd_kernel, bf16_t, grid);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type; RD_FZ4(bn_frozen_bwd_kernel, grid); });
 #undef RD_FZ_TAIL
 #undef RD_FZ4
 #undef RD_FZ
 }
 
 void launch_act_bwd(const void* dz, const void* z, void* dx, int64_t n, int act, float slope, int dtype, hipStream_t st) {
-  if (dtype == 0) hipLaunchKernelGGL((act_bwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)dz, (const float*)z, (float*)dx, n, act, slope);
-  else hipLaunchKernelGGL((act_bwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)z, (bf16_t*)dx, n, act, slope);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((act_bwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)dz, (const T*)z, (T*)dx, n, act, slope); });
 }
 
 // LayerNorm parameter gradients of MANY layer applications in one launch.  An item is one (gamma, beta) pair with the partial buffers of
@@ -1188,25 +1181,23 @@ void launch_colsum(const void* x, float* partial, float* out, int accumulate, in
   int nr = red_rows(rows, C);
   dim3 grid(nr, g.nchunk);
   if (vec_ok(C, dtype)) {
-    if (dtype == 0) hipLaunchKernelGGL((col_reduce_vec_kernel<float, 1, false, -1>), dim3(nr), dim3(256), 0, st, (const float*)x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, 0, 0.f, (const float*)nullptr, (const float*)nullptr);
-    else hipLaunchKernelGGL((col_reduce_vec_kernel<bf16_t, 1, false, -1>), dim3(nr), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, 0, 0.f, (const float*)nullptr, (const float*)nullptr);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((col_reduce_vec_kernel<T, 1, false, -1>), dim3(nr), dim3(256), 0, st, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, 0, 0.f, (const float*)nullptr, (const float*)nullptr); });
   } else if (gen_ok(C, dtype)) {
-    if (dtype == 0) hipLaunchKernelGGL((col_reduce_gen_kernel<float, 1, false, -1>), dim3(nr), dim3(256), 0, st, (const float*)x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, 0, 0.f, (const float*)nullptr, (const float*)nullptr);
-    else hipLaunchKernelGGL((col_reduce_gen_kernel<bf16_t, 1, false, -1>), dim3(nr), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, 0, 0.f, (const float*)nullptr, (const float*)nullptr);
-  } else if (dtype == 0)
-    hipLaunchKernelGGL((col_reduce_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, g.CB, g.PL, 0, 0.f);
-  else
-    hipLaunchKernelGGL((col_reduce_kernel<bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, g.CB, g.PL, 0, 0.f);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((col_reduce_gen_kernel<T, 1, false, -1>), dim3(nr), dim3(256), 0, st, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, 0, 0.f, (const float*)nullptr, (const float*)nullptr); });
+  } else {
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((col_reduce_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, partial, rows, C, g.CB, g.PL, 0, 0.f); });
+  }
   if (out) hipLaunchKernelGGL(colsum_finalize_kernel, dim3((unsigned)C), dim3(64), 0, st, partial, nr, C, out, accumulate);      // out == nullptr: partial rows only
 }
 
 void launch_layernorm_fwd(const void* x, const float* gamma, const float* beta, const void* res, void* out, float* mean,
                           float* rstd, int64_t rows, int C, float eps, int dtype, hipStream_t st) {
   unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(rows, 4), 2048));
-  if (dtype == 0)
-    hipLaunchKernelGGL((layernorm_fwd_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)x, gamma, beta, (const float*)res, (float*)out, mean, rstd, rows, C, eps);
-  else
-    hipLaunchKernelGGL((layernorm_fwd_kernel<bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)x, gamma, beta, (const bf16_t*)res, (bf16_t*)out, mean, rstd, rows, C, eps);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((layernorm_fwd_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)x, gamma, beta, (const T*)res, (T*)out, mean, rstd, rows, C, eps); });
 }
 
 int layernorm_bwd_rows(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(rows, 16), 512)); }
@@ -1215,10 +1206,8 @@ void launch_layernorm_bwd(const void* dout, const void* x, const float* gamma, c
                           float* partial, float* dgamma, float* dbeta, int accumulate, int64_t rows, int C, int dtype,
                           hipStream_t st) {
   int nb = layernorm_bwd_rows(rows);
-  if (dtype == 0)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)dout, (const float*)x, gamma, mean, rstd, (float*)dx, partial, rows, C);
-  else
-    hipLaunchKernelGGL((layernorm_bwd_kernel<bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)x, gamma, mean, rstd, (bf16_t*)dx, partial, rows, C);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(nb), dim3(256), 0, st, (const T*)dout, (const T*)x, gamma, mean, rstd, (T*)dx, partial, rows, C); });
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)C), dim3(256), 0, st, partial, nb, C, 1.0, dgamma, dbeta, accumulate, (float*)nullptr, (float*)nullptr, C);
 }
 

@@ -666,42 +666,42 @@ static unsigned ew_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::
 void launch_maxpool_fwd(const void* x, void* out, unsigned char* arg, int N, int H, int W, int C, int OH, int OW, int k, int s,
                         int p, int dtype, hipStream_t st) {
   int64_t n = (int64_t)N * OH * OW * C;
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   if (C % ve == 0 && (reinterpret_cast<uintptr_t>(arg) & 3) == 0) {
     const unsigned gv = ew_grid(n / ve);
-    if (dtype == 0) hipLaunchKernelGGL((maxpool_fwd_vec_kernel<float>), dim3(gv), dim3(256), 0, st, (const float*)x, (float*)out, arg, N, H, W, C, OH, OW, k, s, p);
-    else hipLaunchKernelGGL((maxpool_fwd_vec_kernel<bf16_t>), dim3(gv), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)out, arg, N, H, W, C, OH, OW, k, s, p);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((maxpool_fwd_vec_kernel<T>), dim3(gv), dim3(256), 0, st, (const T*)x, (T*)out, arg, N, H, W, C, OH, OW, k, s, p); });
     return;
   }
-  if (dtype == 0) hipLaunchKernelGGL((maxpool_fwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)x, (float*)out, arg, N, H, W, C, OH, OW, k, s, p);
-  else hipLaunchKernelGGL((maxpool_fwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)out, arg, N, H, W, C, OH, OW, k, s, p);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)x, (T*)out, arg, N, H, W, C, OH, OW, k, s, p); });
 }
 void launch_maxpool_bwd(const void* dout, const unsigned char* arg, void* dx, int N, int H, int W, int C, int OH, int OW, int k,
                         int s, int p, int dtype, hipStream_t st) {
   int64_t n = (int64_t)N * H * W * C;
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   if (C % ve == 0) {
     unsigned gv = ew_grid(n / ve);
-    if (dtype == 0) hipLaunchKernelGGL((maxpool_bwd_vec_kernel<float>), dim3(gv), dim3(256), 0, st, (const float*)dout, arg, (float*)dx, N, H, W, C, OH, OW, k, s, p);
-    else hipLaunchKernelGGL((maxpool_bwd_vec_kernel<bf16_t>), dim3(gv), dim3(256), 0, st, (const bf16_t*)dout, arg, (bf16_t*)dx, N, H, W, C, OH, OW, k, s, p);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((maxpool_bwd_vec_kernel<T>), dim3(gv), dim3(256), 0, st, (const T*)dout, arg, (T*)dx, N, H, W, C, OH, OW, k, s, p); });
     return;
   }
-  if (dtype == 0) hipLaunchKernelGGL((maxpool_bwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)dout, arg, (float*)dx, N, H, W, C, OH, OW, k, s, p);
-  else hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)dout, arg, (bf16_t*)dx, N, H, W, C, OH, OW, k, s, p);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)dout, arg, (T*)dx, N, H, W, C, OH, OW, k, s, p); });
 }
 void launch_roi_pool_fwd(const void* x, const float* rois, void* out, int* argmax, int R, int N, int H, int W, int C, int PH,
                          int PW, float scale, int dtype, hipStream_t st) {
   int64_t n = (int64_t)R * PH * PW * C;
   if (n == 0) return;
-  const int ve = dtype == 0 ? 4 : 8;
+  const int ve = elem_vec(dtype);
   if (C % ve == 0) {
     unsigned gv = ew_grid(n / ve);
-    if (dtype == 0) hipLaunchKernelGGL((roi_pool_fwd_vec_kernel<float, int>), dim3(gv), dim3(256), 0, st, (const float*)x, rois, (float*)out, argmax, R, N, H, W, C, PH, PW, scale, (int*)nullptr);
-    else hipLaunchKernelGGL((roi_pool_fwd_vec_kernel<bf16_t, int>), dim3(gv), dim3(256), 0, st, (const bf16_t*)x, rois, (bf16_t*)out, argmax, R, N, H, W, C, PH, PW, scale, (int*)nullptr);
+    with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((roi_pool_fwd_vec_kernel<T, int>), dim3(gv), dim3(256), 0, st, (const T*)x, rois, (T*)out, argmax, R, N, H, W, C, PH, PW, scale, (int*)nullptr); });
     return;
   }
-  if (dtype == 0) hipLaunchKernelGGL((roi_pool_fwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)x, rois, (float*)out, argmax, R, N, H, W, C, PH, PW, scale);
-  else hipLaunchKernelGGL((roi_pool_fwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)x, rois, (bf16_t*)out, argmax, R, N, H, W, C, PH, PW, scale);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((roi_pool_fwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)x, rois, (T*)out, argmax, R, N, H, W, C, PH, PW, scale); });
 }
 void launch_roi_pool_bwd(const void* dout, const float* rois, const int* argmax, float* dx_f32, int R, int N, int H, int W, int C,
                          int PH, int PW, int dtype, hipStream_t st) {
@@ -709,23 +709,23 @@ void launch_roi_pool_bwd(const void* dout, const float* rois, const int* argmax,
   hipLaunchKernelGGL(zero_f32_kernel, dim3(ew_grid(nz / 4 + 1)), dim3(256), 0, st, dx_f32, nz);
   int64_t n = (int64_t)R * PH * PW * C;
   if (n == 0) return;
-  if (dtype == 0) hipLaunchKernelGGL((roi_pool_bwd_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)dout, rois, argmax, dx_f32, R, N, H, W, C, PH, PW);
-  else hipLaunchKernelGGL((roi_pool_bwd_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)dout, rois, argmax, dx_f32, R, N, H, W, C, PH, PW);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((roi_pool_bwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)dout, rois, argmax, dx_f32, R, N, H, W, C, PH, PW); });
 }
 
 void launch_roi_pool_bwd_tile(const void* dout, const float* rois, const int* argmax, void* dx, int R, int N, int H, int W, int C,
                               int PH, int PW, float scale, int dtype, hipStream_t st) {
   const int tilesH = (int)cdiv(H, RPB_T), tilesW = (int)cdiv(W, RPB_T);
   dim3 grid((unsigned)(tilesH * tilesW), (unsigned)N, (unsigned)(C / RPT_CC));
-  if (dtype == 0) hipLaunchKernelGGL((roi_pool_bwd_tile_kernel<float>), grid, dim3(256), 0, st, (const float*)dout, rois, argmax, (float*)dx, R, H, W, C, PH, PW, scale, tilesW);
-  else hipLaunchKernelGGL((roi_pool_bwd_tile_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)dout, rois, argmax, (bf16_t*)dx, R, H, W, C, PH, PW, scale, tilesW);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((roi_pool_bwd_tile_kernel<T>), grid, dim3(256), 0, st, (const T*)dout, rois, argmax, (T*)dx, R, H, W, C, PH, PW, scale, tilesW); });
 }
 void launch_roi_pool_bwd_gather(const void* dout, const float* rois, const int* argmax, void* dx, int R, int N, int H, int W, int C,
                                 int PH, int PW, float scale, int dtype, hipStream_t st) {
   const int tilesH = (int)cdiv(H, RPB_T), tilesW = (int)cdiv(W, RPB_T);
   dim3 grid((unsigned)(tilesH * tilesW), (unsigned)N, (unsigned)cdiv(C, RPT_CC));
-  if (dtype == 0) hipLaunchKernelGGL((roi_pool_bwd_pix_kernel<float, int>), grid, dim3(256), 0, st, (const float*)dout, rois, argmax, (float*)dx, R, H, W, C, PH, PW, scale, tilesW, (const int*)nullptr);
-  else hipLaunchKernelGGL((roi_pool_bwd_pix_kernel<bf16_t, int>), grid, dim3(256), 0, st, (const bf16_t*)dout, rois, argmax, (bf16_t*)dx, R, H, W, C, PH, PW, scale, tilesW, (const int*)nullptr);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((roi_pool_bwd_pix_kernel<T, int>), grid, dim3(256), 0, st, (const T*)dout, rois, argmax, (T*)dx, R, H, W, C, PH, PW, scale, tilesW, (const int*)nullptr); });
 }
 
 // ---- compact (one byte per element) arg-max forms: C must be a multiple of the 16-byte vector -----------------------------------------
@@ -733,9 +733,9 @@ void launch_roi_pool_fwd_u8(const void* x, const float* rois, void* out, unsigne
                             int PH, int PW, float scale, int dtype, hipStream_t st) {
   const int64_t n = (int64_t)R * PH * PW * C;
   if (n == 0) return;
-  const unsigned gv = ew_grid(n / (dtype == 0 ? 4 : 8));
-  if (dtype == 0) hipLaunchKernelGGL((roi_pool_fwd_vec_kernel<float, unsigned char>), dim3(gv), dim3(256), 0, st, (const float*)x, rois, (float*)out, argmax, R, N, H, W, C, PH, PW, scale, flag);
-  else hipLaunchKernelGGL((roi_pool_fwd_vec_kernel<bf16_t, unsigned char>), dim3(gv), dim3(256), 0, st, (const bf16_t*)x, rois, (bf16_t*)out, argmax, R, N, H, W, C, PH, PW, scale, flag);
+  const unsigned gv = ew_grid(n / elem_vec(dtype));
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((roi_pool_fwd_vec_kernel<T, unsigned char>), dim3(gv), dim3(256), 0, st, (const T*)x, rois, (T*)out, argmax, R, N, H, W, C, PH, PW, scale, flag); });
 }
 void launch_roi_pool_bwd_u8(const void* dout, const float* rois, const unsigned char* argmax, const int* flag, float* dx_f32, int R, int N, int H,
                             int W, int C, int PH, int PW, float scale, int dtype, hipStream_t st) {
@@ -743,15 +743,15 @@ void launch_roi_pool_bwd_u8(const void* dout, const float* rois, const unsigned 
   hipLaunchKernelGGL(zero_f32_kernel, dim3(ew_grid(nz / 4 + 1)), dim3(256), 0, st, dx_f32, nz);
   const int64_t n = (int64_t)R * PH * PW * C;
   if (n == 0) return;
-  if (dtype == 0) hipLaunchKernelGGL((roi_pool_bwd_u8_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)dout, rois, argmax, flag, dx_f32, R, N, H, W, C, PH, PW, scale);
-  else hipLaunchKernelGGL((roi_pool_bwd_u8_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)dout, rois, argmax, flag, dx_f32, R, N, H, W, C, PH, PW, scale);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((roi_pool_bwd_u8_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)dout, rois, argmax, flag, dx_f32, R, N, H, W, C, PH, PW, scale); });
 }
 void launch_roi_pool_bwd_gather_u8(const void* dout, const float* rois, const unsigned char* argmax, const int* flag, void* dx, int R, int N, int H,
                                    int W, int C, int PH, int PW, float scale, int dtype, hipStream_t st) {
   const int tilesH = (int)cdiv(H, RPB_T), tilesW = (int)cdiv(W, RPB_T);
   dim3 grid((unsigned)(tilesH * tilesW), (unsigned)N, (unsigned)cdiv(C, RPT_CC));
-  if (dtype == 0) hipLaunchKernelGGL((roi_pool_bwd_pix_kernel<float, unsigned char>), grid, dim3(256), 0, st, (const float*)dout, rois, argmax, (float*)dx, R, H, W, C, PH, PW, scale, tilesW, flag);
-  else hipLaunchKernelGGL((roi_pool_bwd_pix_kernel<bf16_t, unsigned char>), grid, dim3(256), 0, st, (const bf16_t*)dout, rois, argmax, (bf16_t*)dx, R, H, W, C, PH, PW, scale, tilesW, flag);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((roi_pool_bwd_pix_kernel<T, unsigned char>), grid, dim3(256), 0, st, (const T*)dout, rois, argmax, (T*)dx, R, H, W, C, PH, PW, scale, tilesW, flag); });
 }
 
 }  // namespace rd

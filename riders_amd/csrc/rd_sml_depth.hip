@@ -134,16 +134,16 @@ static bool aligned16(const void* a, const void* b, const void* c = nullptr) {
 }
 
 void launch_sml_depth_head_fwd(const void* out, float* pred, int64_t n, float hi, float lo, int dtype, hipStream_t st) {
-  const int64_t nv = aligned16(out, pred) ? n / (dtype == 0 ? 4 : 8) : 0;
+  const int64_t nv = aligned16(out, pred) ? n / elem_vec(dtype) : 0;
   const unsigned grid = stream_grid(std::max<int64_t>(nv, nv ? 0 : n));
-  if (dtype == 0) hipLaunchKernelGGL((sml_depth_head_fwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)out, pred, n, nv, hi, lo);
-  else hipLaunchKernelGGL((sml_depth_head_fwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)out, pred, n, nv, hi, lo);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((sml_depth_head_fwd_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)out, pred, n, nv, hi, lo); });
 }
 void launch_sml_depth_head_bwd(const void* out, const float* dpred, void* dout, int64_t n, float hi, float lo, int dtype, hipStream_t st) {
-  const int64_t nv = aligned16(out, dpred, dout) ? n / (dtype == 0 ? 4 : 8) : 0;
+  const int64_t nv = aligned16(out, dpred, dout) ? n / elem_vec(dtype) : 0;
   const unsigned grid = stream_grid(std::max<int64_t>(nv, nv ? 0 : n));
-  if (dtype == 0) hipLaunchKernelGGL((sml_depth_head_bwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)out, dpred, (float*)dout, n, nv, hi, lo);
-  else hipLaunchKernelGGL((sml_depth_head_bwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)out, dpred, (bf16_t*)dout, n, nv, hi, lo);
+  with_elem(dtype, [&](auto e) { using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((sml_depth_head_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)out, dpred, (T*)dout, n, nv, hi, lo); });
 }
 void launch_maxpool_dilate(const float* x, float* y, int N, int H, int W, int k, hipStream_t st) {
   const bool vec = (W & 3) == 0 && aligned16(x, y);
